@@ -13,7 +13,11 @@ resident in HBM.  With N GPUs the film's rows are split into N bands (strong sca
 2-row filter halo); the bands are gathered on rank 0 with one RCCL collective inside the timed region.
 `value` = BVH queries (extension + shadow + MIS rays) of the frame / step time; halo rows a band re-traces are not counted.
 
-The timed steps run the library's default path (no per-launch events).  The JSON line carries
+The timed steps run the library's default path (no per-launch events).  A plain run sets up (one untimed frame: the first
+render call uploads the scene and allocates the workspace), warms up, times the steps and prints the JSON line: `value`,
+`ms_per_step` and the launch configuration of the timed path.  `--dump-outputs DIR` writes what the last timed step computed
+(DIR/film.npy: the (H, W, 4) float32 film, rgb sums and filter weight; DIR/ray_counts.npy: its extension / shadow / MIS rays and
+samples as float64).  With `--full` the line also carries
   roofline     -- per kernel class (traversal = k_extend* + k_connect*, shade = k_shade*): launch durations from HIP events
                   of ONE extra untimed frame on a single pipeline lane (a kernel has the GPU to itself), combined with the
                   hardware counters of the same kernels committed under profiles/ (rocprofv3 --pmc passes of
@@ -30,6 +34,8 @@ The timed steps run the library's default path (no per-launch events).  The JSON
                   cores on a bounded band of the same frame.
   film_check   -- rows of the film the timed steps produced, compared with a committed oracle fixture
                   (tests/golden/bench_*_rows.npz, made by tests/golden/make_golden.py).
+  collective_smoke -- N = 1: RCCL brought up at world size 1 in a child process.
+and, for N > 1, what the band planner's probe render costs (band_probe_ms).
 """
 import argparse
 import importlib
@@ -58,6 +64,23 @@ PMC_FILE = os.path.join(ROOT, "profiles", "r04_pmc_%s.json")
 CEILING_FILE = os.path.join(ROOT, "profiles", "r03_valu_ceiling.json")
 CALIB_FILE = os.path.join(ROOT, "profiles", "r04_fetch_calib.json")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "bench_%s_rows.npz")
+DUMP_LIMIT = 64 << 20                      # --dump-outputs: bytes in all
+
+
+def seeded_sample(n, k, seed=0):
+    """k of the indices 0..n-1, the same ones every run (sorted); all of them when k >= n."""
+    import numpy as np
+    return np.arange(n) if k >= n else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array (float32 / float64) as out_dir/<name>.npy."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cores():
@@ -381,11 +404,14 @@ def trace_main(args):
         j = json.load(open(pmc_path))
         if j.get("_meta", {}).get("source_hash") == src_hash:
             pmc = next((v for k, v in j.items() if k.startswith("k_extend_rf")), None)
-    res_sets = {}
+    res_sets, outputs = {}, {}
     for label, rays in sets.items():
         pkg.trace_bench(scene, rays, repeats=max(args.warmup, 1))
         st, hits = pkg.trace_bench(scene, rays, repeats=args.steps, want_hits=True)
         n = len(rays)
+        if args.dump_outputs:  # 2 x 512 k hits x 5 float64 = 40 MiB
+            h = hits[seeded_sample(n, 1 << 19)]
+            outputs["hits_round%s" % label.split("round ")[1].rstrip(")")] = np.stack([h[f].astype(np.float64) for f in ("prim", "t", "b0", "b1", "b2")], axis=1)
         check, _ = pkg.trace_rays(scene, rays[:200000])
         same = bool(np.array_equal(check["prim"], hits["prim"][:200000]) and np.array_equal(check["b1"].view(np.uint32), hits["b1"][:200000].view(np.uint32)))
         npr, tpr = st.nodes_visited / n, st.tris_tested / n
@@ -427,6 +453,8 @@ def trace_main(args):
            "config": {"workload": "%s: k_extend_rf over the extension rays of round 0 and round 3 of a %dx%d, 16 spp frame (stand-in scene for BASELINE configs[%d])" % (args.workload, res[0], res[1], 2 if name == "colonnade" else 3),
                       "node_order": pkg.get_option("node_order"), "options": {k: pkg.get_option(k) for k in ("grid_mult", "refill", "vote", "stack_lds")}},
            "roofline": roof}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(out))
 
 
@@ -439,8 +467,11 @@ def main():
     ap.add_argument("--res", type=int, default=0, help="cornell only: square resolution")
     ap.add_argument("--depth", type=int, default=DEPTH)
     ap.add_argument("--paths-per-pass", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-collective-smoke", action="store_true", help="N = 1: skip the child process that brings up RCCL at world size 1 and runs the film gather")
+    ap.add_argument("--full", action="store_true", help="beside the headline: roofline (counter frame, single-lane frame, HBM copy rate), film check against the committed fixture, "
+                                                        "CPU baseline, RCCL smoke; N > 1: the band probe's cost")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-collective-smoke", action="store_true", help="--full, N = 1: skip the child process that brings up RCCL at world size 1 and runs the film gather")
     ap.add_argument("--even-bands", action="store_true", help="N > 1: bands of equal height instead of equal cost")
     ap.add_argument("--rehearse", action="store_true", help="the multi-rank plumbing only (launch, process group, band plan, film gather), no render: runs without a GPU over gloo")
     ap.add_argument("--profile", action="store_true", help="for rocprofv3 runs: render exactly --steps frames on ONE pipeline lane (no counter / warm-up frames, no JSON)")
@@ -452,6 +483,8 @@ def main():
     ap.add_argument("--workload", default="cornell", choices=sorted(WORKLOADS) + sorted(TRACE_WORKLOADS),
                     help="cornell = BASELINE configs[1] (the headline); colonnade / classroom = synthetic stand-ins for configs[2] / [3]")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload in TRACE_WORKLOADS:
         return trace_main(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher around us: be the launcher (before torch is imported, before any GPU call)
@@ -493,12 +526,13 @@ def main():
     integ.preprocess(scene)
     # N > 1: bands of equal cost (per-row ray counts of ONE untimed 1-spp probe render with device counters; every rank computes the same
     # plan), unless --even-bands or the plan would take less than 1 % off the slowest band
-    bounds, probe_ms, plan_gain = None, 0.0, None
+    bounds, probe_ms, plan_gain = None, (0.0 if args.full else None), None
     if world > 1 and not args.even_bands:
         cost = par.probe_row_cost(pkg, cam, scene, args.depth, device=local_rank, spp=1)  # (the process's first call into the library: scene upload and workspace allocation ride on it)
-        torch.cuda.synchronize(); tp = time.perf_counter()
-        par.probe_row_cost(pkg, cam, scene, args.depth, device=local_rank, spp=1, cache=False)  # what the probe itself costs (a host that plans a NEW view pays this once; the same view again comes out of the cache)
-        torch.cuda.synchronize(); probe_ms = (time.perf_counter() - tp) * 1e3
+        if args.full:
+            torch.cuda.synchronize(); tp = time.perf_counter()
+            par.probe_row_cost(pkg, cam, scene, args.depth, device=local_rank, spp=1, cache=False)  # what the probe itself costs (a host that plans a NEW view pays this once; the same view again comes out of the cache)
+            torch.cuda.synchronize(); probe_ms = (time.perf_counter() - tp) * 1e3
         plan_gain = par.plan_gain(H, world, cost)
         if plan_gain >= 1.01:
             bounds = par.plan_bands(H, world, cost)
@@ -563,16 +597,18 @@ def main():
             sync()
         print("profile frames: %d, rays per frame %d, kernel launches per frame %d" % (args.steps, st.rays, st.kernel_launches))
         return
-    lanes = pkg.get_option("lanes")
-    # untimed: counters for the algorithmic per-ray node / triangle averages
-    cst = step(pkg.abi.FLAG_COUNTERS)
-    c_rays = cst.rays
-    nodes_per_ray, tris_per_ray = cst.nodes_visited / max(c_rays, 1), cst.tris_tested / max(c_rays, 1)
-    # untimed: one frame on a single pipeline lane with an event pair around every launch, so that no two kernels share the
-    # machine -- each kernel class's own duration
-    with pkg.options(lanes=1):
-        xst = step(pkg.abi.FLAG_TIMING)
-        sync()
+    if args.full:
+        # untimed: counters for the algorithmic per-ray node / triangle averages
+        cst = step(pkg.abi.FLAG_COUNTERS)
+        c_rays = cst.rays
+        nodes_per_ray, tris_per_ray = cst.nodes_visited / max(c_rays, 1), cst.tris_tested / max(c_rays, 1)
+        # untimed: one frame on a single pipeline lane with an event pair around every launch, so that no two kernels share the
+        # machine -- each kernel class's own duration
+        with pkg.options(lanes=1):
+            xst = step(pkg.abi.FLAG_TIMING)
+            sync()
+    else:
+        step(0)  # set-up: the first render call uploads the scene and allocates the workspace
     for _ in range(args.warmup):
         step(0)
     sync()
@@ -600,55 +636,12 @@ def main():
     else:
         rays, samples, rays_traced, rows_traced = float(vals[1]), float(vals[2]), float(vals[3]), float(vals[4])
     if rank == 0:
-        b_ray = 32.0 + 32.0 * nodes_per_ray + 48.0 * tris_per_ray + 16.0
-        src_hash = pkg.build_id()  # the id the LOADED library was built with (sources + every compiler flag)
-        pmc, pmc_meta = load_pmc(args.workload, src_hash) if (world == 1 and standard) else (None, {"file": None, "why": "counters are per frame of the standard single-GPU workload"})
-        classes = {
-            "traversal": class_roofline("traversal", xst.ms_extend + xst.ms_connect, xst.extend_launches + xst.connect_launches, pmc, algorithmic_bytes=xst.rays * b_ray),
-            "shade": class_roofline("shade", xst.ms_shade_kernels, xst.shade_launches, pmc),
-            "tail": class_roofline("tail", xst.ms_tail, xst.tail_launches, pmc),
-        }
-        dom = max(classes, key=lambda k: classes[k]["ms_per_frame_single_lane"])
-        d = classes[dom]
-        ceiling = None
-        if os.path.exists(CEILING_FILE):
-            cj = json.load(open(CEILING_FILE))
-            pick = lambda inst: max((r["per_cycle_per_simd"] for r in cj["rows"] if r["inst"] == inst and r["chains"].startswith("8")), default=None)
-            ceiling = {"file": os.path.relpath(CEILING_FILE, ROOT), "per_cycle_per_simd": {k: pick(k) for k in ("v_fma_f32", "v_mul_f32", "v_add_f32", "v_max_f32", "v_cndmask_b32_e64 (mask in an SGPR pair)", "v_cmp_lt_f32_e64 -> SGPR pair", "v_fma_f64")},
-                       "what": "measured wave64 issue rates on MI355X (tools/valu_ceiling.hip): fp32 add / mul / fma ~0.45 per cycle and SIMD, comparison / select / min-max class ~0.24; a mix of both classes issues side by side"}
-        roof = {
-            "kernel": "%s kernels (%s)" % (dom, ", ".join(d["counters"]["kernels"]) if d.get("counters") else ("k_extend_rf + k_connect_rf" if dom == "traversal" else "k_shade<material, features>")),
-            "bound": d.get("bound"),
-            "why": "neither class moves more than a fraction of the HBM peak (hbm.frac); the scarce resource is vector issue: `frac` is the share of the SIMDs' vector-ALU time the class's instructions need at the measured gfx950 issue rates (valu_ceiling), the rest of a wave's time is s_waitcnt (wave_wait_frac) -- dependent chains inside a wave (LDS reads -> slab test -> stack) that more resident waves did NOT shorten (DESIGN 4.1)",
-            "achieved": d.get("valu_ginst_per_s"), "peak": d.get("valu_ceiling_ginst_per_s"), "unit": "G wave64 VALU instructions/s (peak = what 1024 SIMDs issue of this class's instruction mix at the measured rates)",
-            "frac": d.get("valu_pipe_frac"), "frac_lo_hi": d.get("valu_pipe_frac_lo_hi"),
-            "wave": {"issue": d.get("wave_issue_frac"), "wait": d.get("wave_wait_frac"), "stall": d.get("wave_stall_frac"), "salu_per_valu": d.get("salu_per_valu"), "lanes_per_valu_inst": d.get("lanes_per_valu_inst"),
-                     "lds_busy": d.get("lds_busy_frac"), "lds_conflict_share": d.get("lds_conflict_share")},
-            "traffic": d.get("hbm_bytes_per_launch"),
-            "hbm": {"achieved": d.get("hbm_counter_gbs"), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d.get("hbm_counter_frac"), "what": "2 x FETCH_SIZE + WRITE_SIZE of the class's kernels (committed rocprofv3 PMC passes; FETCH_SIZE calibrated: profiles/r04_fetch_calib.json) / their single-lane duration measured in this run: bytes below L2 (HBM + Infinity Cache)"},
-            "algorithmic": {"what": "SURVEY 8(d): 32 B ray in + 32 B per box tested + 48 B per triangle tested + 16 B hit out, x rays / traversal-kernel time; NOT HBM traffic (LDS- and L2-served)",
-                            "bytes_per_ray": b_ray, "nodes_per_ray": nodes_per_ray, "tris_per_ray": tris_per_ray, "gbs": classes["traversal"].get("algorithmic_gbs"), "frac_of_hbm_peak": classes["traversal"].get("algorithmic_frac_of_hbm_peak"),
-                            "bytes_per_launch": xst.rays * b_ray / max(xst.extend_launches + xst.connect_launches, 1)},
-            "classes": classes, "valu_ceiling": ceiling,
-            "counters_from": pmc_meta, "counters_usable": bool(d.get("valu_pipe_frac") is not None),
-            "timing": "HIP events around every launch of ONE untimed frame on a single pipeline lane (ms_per_frame_single_lane); the timed steps run the default path on %d lanes without events" % int(st.lanes),
-            "single_lane_frame_ms": {"extend": xst.ms_extend, "connect": xst.ms_connect, "shade": xst.ms_shade_kernels, "aux (generate, epilogue, resolve)": xst.ms_aux, "film": xst.ms_film, "tail (fused late rounds)": xst.ms_tail},
-            "b_state_bytes_per_path_round": 216, "hbm_copy_measured_gbs": hbm_copy_gbs(torch, dev),
-        }
-        # film check: rows of the timed film against the committed oracle fixture
-        film_check = "no fixture for these settings"
-        gpu_rows = None
-        fx = FIXTURE % args.workload
-        if standard and os.path.exists(fx):
-            z = np.load(fx)
-            r0, r1 = int(z["row0"]), int(z["row1"])
-            got = film[r0:r1].cpu().numpy().astype(np.float64)
-            ref = z["film"].astype(np.float64)
-            rel = float(np.sqrt(((got - ref) ** 2).sum() / max((ref ** 2).sum(), 1e-30)))
-            film_check = "ok" if rel < 1e-5 else "MISMATCH"
-            roof_rel = rel
-        else:
-            roof_rel = None
+        if args.dump_outputs:
+            rows = seeded_sample(H, (DUMP_LIMIT >> 1) // (W * 16))  # the whole film, or a seeded sample of its rows if it is larger than half the limit
+            outputs = {"film": film.cpu().numpy()[rows], "ray_counts": np.array([st.rays_extension, st.rays_shadow, st.rays_mis, st.samples], dtype=np.float64)}
+            if len(rows) < H:
+                outputs["film_rows"] = rows.astype(np.float64)
+            dump_outputs(args.dump_outputs, outputs)
         out = {
             "metric": "Mray/s, %s %dx%d, %d spp, depth %d (Msample/s in config)" % (wl["metric"] % scene.num_triangles() if "%d" in wl["metric"] else wl["metric"], W, H, spp, args.depth),
             "value": rays / dt / 1e6, "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -658,7 +651,7 @@ def main():
                        "msample_per_s": samples / dt / 1e6, "rays_per_sample": rays / max(samples, 1.0), "row_bands": world,
                        "band_plan": ("single band" if world == 1 else ("equal height" if bounds is None else "equal cost (one 1-spp probe render with a device counter per sample row): rows %s" % (bounds,))),
                        "band_plan_gain_predicted": plan_gain,
-                       "band_probe_ms": probe_ms, "value_incl_band_probe": rays / (dt + args.steps * probe_ms * 1e-3) / 1e6,  # a host that plans its bands per frame pays the probe per frame
+                       "band_probe_ms": probe_ms, "value_incl_band_probe": rays / (dt + args.steps * probe_ms * 1e-3) / 1e6 if probe_ms is not None else None,  # a host that plans its bands per frame pays the probe per frame
                        "dist": {"backend": ("none" if world == 1 else ("rccl" if backend == "nccl" else backend + " (fallback or rehearsal: NOT an RCCL number)")), "world_size": dist.get_world_size() if world > 1 else 1,
                                 "launched_by": launched_by, "gather_mode": gather_mode if world > 1 else None, "gather_preflight": preflight,
                                 "note": "no N > 1 hardware run existed when this was written: the first one is the first execution of the RCCL gather at world size > 1"},
@@ -670,17 +663,66 @@ def main():
                        "launch": {"queue_segments_per_pass": st.queue_segments, "passes_per_frame": st.passes, "kernel_launches_per_frame": st.kernel_launches,
                                   "workgroups_last_launch": dict(zip(("extend", "connect", "shade", "aux"), [int(x) for x in st.grid_wgs])),
                                   "resident_workgroups_per_cu": dict(zip(("extend", "connect", "shade", "aux"), [int(x) for x in st.resident_wgs_per_cu])),
-                                  "fused_tail": {"launches_per_frame": int(st.tail_launches), "from_round": (int(st.tail_round) if st.tail_launches else None),
-                                                 "single_lane_frame": {"launches": int(xst.tail_launches), "from_round": (int(xst.tail_round) if xst.tail_launches else None)}},
+                                  "fused_tail": {"launches_per_frame": int(st.tail_launches), "from_round": (int(st.tail_round) if st.tail_launches else None)},
                                   "options": {k: pkg.get_option(k) for k in ("lanes", "grid_mult", "grid_pct", "persist", "refill", "refill_connect", "vote", "tail", "tail_at", "tail_paths")}}},
-            "roofline": roof,
-            "film_check": film_check, "film_check_rel_l2": roof_rel,
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cornell" and standard:
-            gpu_rows = film[500:628].cpu().numpy()
-            out["cpu_baseline"] = cpu_baseline(pkg, gpu_rows)
-        if world == 1 and not args.no_collective_smoke:
-            out["collective_smoke"] = collective_smoke()
+        if args.full:
+            b_ray = 32.0 + 32.0 * nodes_per_ray + 48.0 * tris_per_ray + 16.0
+            src_hash = pkg.build_id()  # the id the LOADED library was built with (sources + every compiler flag)
+            pmc, pmc_meta = load_pmc(args.workload, src_hash) if (world == 1 and standard) else (None, {"file": None, "why": "counters are per frame of the standard single-GPU workload"})
+            classes = {
+                "traversal": class_roofline("traversal", xst.ms_extend + xst.ms_connect, xst.extend_launches + xst.connect_launches, pmc, algorithmic_bytes=xst.rays * b_ray),
+                "shade": class_roofline("shade", xst.ms_shade_kernels, xst.shade_launches, pmc),
+                "tail": class_roofline("tail", xst.ms_tail, xst.tail_launches, pmc),
+            }
+            dom = max(classes, key=lambda k: classes[k]["ms_per_frame_single_lane"])
+            d = classes[dom]
+            ceiling = None
+            if os.path.exists(CEILING_FILE):
+                cj = json.load(open(CEILING_FILE))
+                pick = lambda inst: max((r["per_cycle_per_simd"] for r in cj["rows"] if r["inst"] == inst and r["chains"].startswith("8")), default=None)
+                ceiling = {"file": os.path.relpath(CEILING_FILE, ROOT), "per_cycle_per_simd": {k: pick(k) for k in ("v_fma_f32", "v_mul_f32", "v_add_f32", "v_max_f32", "v_cndmask_b32_e64 (mask in an SGPR pair)", "v_cmp_lt_f32_e64 -> SGPR pair", "v_fma_f64")},
+                           "what": "measured wave64 issue rates on MI355X (tools/valu_ceiling.hip): fp32 add / mul / fma ~0.45 per cycle and SIMD, comparison / select / min-max class ~0.24; a mix of both classes issues side by side"}
+            roof = {
+                "kernel": "%s kernels (%s)" % (dom, ", ".join(d["counters"]["kernels"]) if d.get("counters") else ("k_extend_rf + k_connect_rf" if dom == "traversal" else "k_shade<material, features>")),
+                "bound": d.get("bound"),
+                "why": "neither class moves more than a fraction of the HBM peak (hbm.frac); the scarce resource is vector issue: `frac` is the share of the SIMDs' vector-ALU time the class's instructions need at the measured gfx950 issue rates (valu_ceiling), the rest of a wave's time is s_waitcnt (wave_wait_frac) -- dependent chains inside a wave (LDS reads -> slab test -> stack) that more resident waves did NOT shorten (DESIGN 4.1)",
+                "achieved": d.get("valu_ginst_per_s"), "peak": d.get("valu_ceiling_ginst_per_s"), "unit": "G wave64 VALU instructions/s (peak = what 1024 SIMDs issue of this class's instruction mix at the measured rates)",
+                "frac": d.get("valu_pipe_frac"), "frac_lo_hi": d.get("valu_pipe_frac_lo_hi"),
+                "wave": {"issue": d.get("wave_issue_frac"), "wait": d.get("wave_wait_frac"), "stall": d.get("wave_stall_frac"), "salu_per_valu": d.get("salu_per_valu"), "lanes_per_valu_inst": d.get("lanes_per_valu_inst"),
+                         "lds_busy": d.get("lds_busy_frac"), "lds_conflict_share": d.get("lds_conflict_share")},
+                "traffic": d.get("hbm_bytes_per_launch"),
+                "hbm": {"achieved": d.get("hbm_counter_gbs"), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d.get("hbm_counter_frac"), "what": "2 x FETCH_SIZE + WRITE_SIZE of the class's kernels (committed rocprofv3 PMC passes; FETCH_SIZE calibrated: profiles/r04_fetch_calib.json) / their single-lane duration measured in this run: bytes below L2 (HBM + Infinity Cache)"},
+                "algorithmic": {"what": "SURVEY 8(d): 32 B ray in + 32 B per box tested + 48 B per triangle tested + 16 B hit out, x rays / traversal-kernel time; NOT HBM traffic (LDS- and L2-served)",
+                                "bytes_per_ray": b_ray, "nodes_per_ray": nodes_per_ray, "tris_per_ray": tris_per_ray, "gbs": classes["traversal"].get("algorithmic_gbs"), "frac_of_hbm_peak": classes["traversal"].get("algorithmic_frac_of_hbm_peak"),
+                                "bytes_per_launch": xst.rays * b_ray / max(xst.extend_launches + xst.connect_launches, 1)},
+                "classes": classes, "valu_ceiling": ceiling,
+                "counters_from": pmc_meta, "counters_usable": bool(d.get("valu_pipe_frac") is not None),
+                "timing": "HIP events around every launch of ONE untimed frame on a single pipeline lane (ms_per_frame_single_lane); the timed steps run the default path on %d lanes without events" % int(st.lanes),
+                "single_lane_frame_ms": {"extend": xst.ms_extend, "connect": xst.ms_connect, "shade": xst.ms_shade_kernels, "aux (generate, epilogue, resolve)": xst.ms_aux, "film": xst.ms_film, "tail (fused late rounds)": xst.ms_tail},
+                "b_state_bytes_per_path_round": 216, "hbm_copy_measured_gbs": hbm_copy_gbs(torch, dev),
+            }
+            # film check: rows of the timed film against the committed oracle fixture
+            film_check = "no fixture for these settings"
+            gpu_rows = None
+            fx = FIXTURE % args.workload
+            if standard and os.path.exists(fx):
+                z = np.load(fx)
+                r0, r1 = int(z["row0"]), int(z["row1"])
+                got = film[r0:r1].cpu().numpy().astype(np.float64)
+                ref = z["film"].astype(np.float64)
+                rel = float(np.sqrt(((got - ref) ** 2).sum() / max((ref ** 2).sum(), 1e-30)))
+                film_check = "ok" if rel < 1e-5 else "MISMATCH"
+                roof_rel = rel
+            else:
+                roof_rel = None
+            out["config"]["launch"]["fused_tail"]["single_lane_frame"] = {"launches": int(xst.tail_launches), "from_round": (int(xst.tail_round) if xst.tail_launches else None)}
+            out.update(roofline=roof, film_check=film_check, film_check_rel_l2=roof_rel)
+            if world == 1 and not args.no_cpu_baseline and args.workload == "cornell" and standard:
+                gpu_rows = film[500:628].cpu().numpy()
+                out["cpu_baseline"] = cpu_baseline(pkg, gpu_rows)
+            if world == 1 and not args.no_collective_smoke:
+                out["collective_smoke"] = collective_smoke()
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -8,7 +8,7 @@ for i in $(seq $N); do
   for L in $A $B; do
     for W in ${WORKLOADS:-cornell colonnade classroom}; do
       echo "## $L $W" >> $OUT
-      PTRS_LIB=$L python bench.py --workload $W --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-collective-smoke 2>> gpurun_out/ablib_$TAG.err | python -c "
+      PTRS_LIB=$L python bench.py --workload $W --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-collective-smoke --full 2>> ${OUT%.txt}.err | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ for i in $(seq $N); do
   for E in "$A" "$B"; do
     for W in ${WORKLOADS:-cornell colonnade classroom}; do
       echo "## $E $W" >> $OUT
-      env $E python bench.py --workload $W --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-collective-smoke 2>> gpurun_out/abopt_$TAG.err | python -c "
+      env $E python bench.py --workload $W --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-collective-smoke --full 2>> ${OUT%.txt}.err | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -15,9 +15,9 @@ for W in cornell colonnade classroom; do
   cp gpurun_out/prof_fin_$W/kernel_stats.csv $OUT/r04_${W}_kernel_stats.csv
   cp gpurun_out/prof_fin_$W/report.txt $OUT/r04_${W}_report.txt
 done
-timeout -k 10 600 python bench.py > $OUT/r04_bench_cornell.json || exit 1
-timeout -k 10 600 python bench.py --workload colonnade --no-collective-smoke > $OUT/r04_bench_colonnade.json || exit 1
-timeout -k 10 600 python bench.py --workload classroom --no-collective-smoke > $OUT/r04_bench_classroom.json || exit 1
+timeout -k 10 600 python bench.py --full > $OUT/r04_bench_cornell.json || exit 1
+timeout -k 10 600 python bench.py --workload colonnade --full --no-collective-smoke > $OUT/r04_bench_colonnade.json || exit 1
+timeout -k 10 600 python bench.py --workload classroom --full --no-collective-smoke > $OUT/r04_bench_classroom.json || exit 1
 if [ -z "$SKIP_TRACE" ]; then tools/trace_profiles.sh || exit 1; fi
 python - <<'PY'
 import json, glob

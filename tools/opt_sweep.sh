@@ -2,7 +2,7 @@
 # tools/opt_sweep.sh WORKLOAD "ENV1" "ENV2" ... -- bench.py once per option setting (PTRS_OPT_* of the Python host): ms per step, one line each
 W=$1; shift
 for E in "$@"; do
-  env $E python bench.py --workload $W --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline --no-collective-smoke 2>/dev/null | python -c "
+  env $E python bench.py --workload $W --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline --no-collective-smoke --full 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
