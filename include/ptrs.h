@@ -358,6 +358,20 @@ int ptrs_sobol_samples(const PtrsRenderParams *params, uint32_t n, const int32_t
 int ptrs_selftest_div3(int32_t device, uint32_t mode, uint64_t n_sets, uint64_t seed, uint64_t *mismatches_out,
                        uint64_t *fast_path_sets_out /* may be NULL */, uint32_t *first_bad_out /* may be NULL */);
 
+/* Known-answer probes (test entry points; the render path does not use them).  They run the device code's
+ * csrc/pt_probe.h, one row per thread, at most PTRS_PROBE_MAX_ROWS rows per call.
+ * ptrs_probe_bsdf: material `material` of the scene (Matte, Metal, Mirror, Glass, Disney or Substrate, constant
+ * textures) at a hit with frame[9] = geometric normal, shading normal, shading dpdu (orthogonal to the shading
+ * normal).  rows: n x 8 floats (wo.xyz, wi.xyz, u.xy, world space); out: n x 16 floats = bsdf.f(wo, wi).rgb,
+ * bsdf.pdf(wo, wi), sample_f(wo, u): f.rgb, pdf, wi.xyz, sampled flags, then 1 when the material yields a BSDF
+ * (0: no BSDF, Q17), 0, 0, 0.
+ * ptrs_probe_light: light `light` of the scene, area (triangle) or environment, seen from ref[6] = point, normal.
+ * rows: n x 5 floats (u.xy, w.xyz); out: n x 16 floats = sample_li(u): wi.xyz, pdf, Li.rgb, ok; pdf_li(w); le(w).rgb;
+ * 0, 0, 0, 0. */
+#define PTRS_PROBE_MAX_ROWS (1u << 24)
+int ptrs_probe_bsdf(PtrsScene *scene, int32_t material, const float *frame, uint32_t n, const float *rows, float *out);
+int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t n, const float *rows, float *out);
+
 #ifdef __cplusplus
 }
 #endif

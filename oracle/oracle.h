@@ -32,6 +32,8 @@ int orc_stratified_tile(uint64_t seed, int32_t tile_w, int32_t tile_h, int32_t d
 void orc_pcg64mcg(uint64_t state_lo, uint64_t state_hi, uint32_t n, uint64_t *out);
 int orc_bsdf_eval(const PtrsMaterial *mat, const float *tex_values, uint32_t n, const float *wo,
                   const float *u, float *out);
+int orc_bsdf_probe(const PtrsMaterial *mat, const float *tex_values, const float *frame, uint32_t n,
+                   const float *in, float *out);
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,25 @@ def bsdf_eval(material, tex_values, wo, u):
     return out
 
 
+def bsdf_probe(material, tex_values, frame, rows):
+    """orc_bsdf_probe: rows (n x 8: wo, wi, u) at a hit with frame (ng, ns, dpdu) -> (n x 16) in the layout of csrc/pt_probe.h."""
+    m = abi.PtrsMaterial()
+    m.kind = material["kind"]
+    tx = list(material.get("tex", [])) + [-1] * 6
+    m.tex[:] = tx[:6]
+    m.flags = material.get("flags", 0)
+    m.inner = -1
+    tv = np.zeros((6, 3), dtype=np.float32)
+    if len(tex_values):
+        tv[: len(tex_values)] = np.asarray(tex_values, dtype=np.float32)
+    fr = np.ascontiguousarray(frame, dtype=np.float32).reshape(9)
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(lib().orc_bsdf_probe(C.byref(m), C.c_void_p(tv.ctypes.data), C.c_void_p(fr.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data),
+                                C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def filter_table():
     t = np.zeros(256, dtype=np.float32)
     lib().orc_filter_table(C.c_void_p(t.ctypes.data))

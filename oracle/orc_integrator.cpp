@@ -491,4 +491,35 @@ int orc_bsdf_eval(const PtrsMaterial *mat, const float *tex_values, uint32_t n, 
     return PTRS_OK;
 }
 
+// The same material at a hit of the caller's frame (geometric normal, shading normal, shading dpdu), per row
+// wo, wi, u: bsdf.f(wo, wi) and bsdf.pdf(wo, wi) besides sample_f -- the row layout of the device code's
+// bsdf_probe_row (csrc/pt_probe.h), so that tests/test_bsdf_kat.py compares the three bit for bit.
+int orc_bsdf_probe(const PtrsMaterial *mat, const float *tex_values, const float *frame, uint32_t n, const float *in /* n*8 */, float *out /* n*16 */) {
+    Scene sc;
+    sc.textures.resize(6);
+    for (int i = 0; i < 6; i++) { sc.textures[i].kind = PTRS_TEX_CONSTANT; for (int c = 0; c < 3; c++) sc.textures[i].value[c] = tex_values[3 * i + c]; }
+    Material m; m.kind = mat->kind; m.flags = mat->flags; m.inner = -1;
+    for (int i = 0; i < 6; i++) m.tex[i] = mat->tex[i] < 0 ? -1 : i;
+    sc.materials.push_back(m);
+    const Vec3 ng(frame[0], frame[1], frame[2]), ns(frame[3], frame[4], frame[5]), dpdu(frame[6], frame[7], frame[8]);
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = in + 8 * (size_t)i;
+        float *o = out + 16 * (size_t)i;
+        for (int k = 0; k < 16; k++) o[k] = 0.0f;
+        const Vec3 wo(r[0], r[1], r[2]), wi_q(r[3], r[4], r[5]);
+        SurfaceInteraction si = SurfaceInteraction::make(Vec3(0, 0, 0), Vec3(), Vec2{0.25f, 0.5f}, wo, Vec3(1, 0, 0), Vec3(0, 1, 0), Vec3(), Vec3(), 0);
+        si.general.n = ng; si.shading.n = ns; si.shading.dpdu = dpdu; si.shading.dpdv = cross(ns, dpdu);
+        BSDF bsdf;
+        if (!compute_scattering_functions(sc, 0, si, bsdf)) continue;
+        Spectrum f = bsdf.f(wo, wi_q, BSDF_ALL);
+        float pdf_q = bsdf.pdf(wo, wi_q, BSDF_ALL);
+        Vec3 wi(0, 0, 0); float pdf = 0.0f; uint32_t flags = 0;
+        Spectrum sf = bsdf.sample_f(wo, wi, Vec2{r[6], r[7]}, pdf, BSDF_ALL, &flags);
+        o[0] = f.r; o[1] = f.g; o[2] = f.b; o[3] = pdf_q;
+        o[4] = sf.r; o[5] = sf.g; o[6] = sf.b; o[7] = pdf;
+        o[8] = wi.x; o[9] = wi.y; o[10] = wi.z; o[11] = (float)flags; o[12] = 1.0f;
+    }
+    return PTRS_OK;
+}
+
 } // extern "C"

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pt_render.h"
+#include "pt_probe.h"
 
 using namespace pt;
 
@@ -1275,6 +1276,19 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_div3(uint64_t seed, uint32_t
     atomicAdd(out + 1, fast);
 }
 
+// Known-answer probes (csrc/pt_probe.h): one row per thread, the same functions the host twin runs.
+struct ProbeArgs { float v[9]; }; // BSDF: ng, ns, dpdu; light: p, n (6 used)
+__global__ __launch_bounds__(BLOCK) void k_probe_bsdf(DScene sc, int32_t mat, int32_t kind, ProbeArgs frame, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    bsdf_probe_row(sc, mat, kind, frame.v, in + (uint64_t)i * PROBE_BSDF_IN, out + (uint64_t)i * PROBE_BSDF_OUT);
+}
+__global__ __launch_bounds__(BLOCK) void k_probe_light(DScene sc, int32_t light, ProbeArgs ref, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    light_probe_row(sc, light, ref.v, in + (uint64_t)i * PROBE_LIGHT_IN, out + (uint64_t)i * PROBE_LIGHT_OUT);
+}
+
 // ---- device buffers ---------------------------------------------------------------------------------
 struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
@@ -2321,6 +2335,52 @@ int ptrs_selftest_div3(int32_t device, uint32_t mode, uint64_t n_sets, uint64_t 
         *mismatches_out = h[0];
         if (fast_path_sets_out) *fast_path_sets_out = h[1];
         if (first_bad_out) std::memcpy(first_bad_out, hb, 40);
+        return PTRS_OK;
+    });
+}
+
+int ptrs_probe_bsdf(PtrsScene *scene, int32_t material, const float *frame, uint32_t n, const float *rows, float *out) {
+    return guarded([&]() -> int {
+        if (!scene || !frame || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        if (material < 0 || (size_t)material >= scene->H.mats.size()) { g_err = "material index out of range"; return PTRS_ERR_INVALID; }
+        const int32_t kind = scene->H.mats[material].kind;
+        if (kind < 0 || kind > 5) { g_err = "the BSDF probe takes Matte, Metal, Mirror, Glass, Disney or Substrate"; return PTRS_ERR_UNSUPPORTED; }
+        ProbeArgs fr; std::memcpy(fr.v, frame, sizeof(fr.v));
+        HIPCHK(hipSetDevice(scene->device));
+        if (n == 0) return PTRS_OK;
+        DevBuf bi, bo;
+        int rc;
+        if ((rc = bi.ensure((size_t)n * PROBE_BSDF_IN * 4)) || (rc = bo.ensure((size_t)n * PROBE_BSDF_OUT * 4))) { bi.release(); bo.release(); return rc; }
+        hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * PROBE_BSDF_IN * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_probe_bsdf, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, scene->sc, material, kind, fr, n, (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * PROBE_BSDF_OUT * 4, hipMemcpyDeviceToHost);
+        bi.release(); bo.release();
+        if (e != hipSuccess) { g_err = std::string("ptrs_probe_bsdf: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+        return PTRS_OK;
+    });
+}
+
+int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t n, const float *rows, float *out) {
+    return guarded([&]() -> int {
+        if (!scene || !ref || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        if (light < 0 || (size_t)light >= scene->H.lights.size()) { g_err = "light index out of range"; return PTRS_ERR_INVALID; }
+        const int32_t kind = scene->H.lights[light].kind;
+        if (kind != 2 && kind != 3) { g_err = "the light probe takes area (triangle) and environment lights"; return PTRS_ERR_UNSUPPORTED; }
+        ProbeArgs rf{}; std::memcpy(rf.v, ref, 6 * sizeof(float));
+        HIPCHK(hipSetDevice(scene->device));
+        if (n == 0) return PTRS_OK;
+        DevBuf bi, bo;
+        int rc;
+        if ((rc = bi.ensure((size_t)n * PROBE_LIGHT_IN * 4)) || (rc = bo.ensure((size_t)n * PROBE_LIGHT_OUT * 4))) { bi.release(); bo.release(); return rc; }
+        hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * PROBE_LIGHT_IN * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_probe_light, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, scene->sc, light, rf, n, (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * PROBE_LIGHT_OUT * 4, hipMemcpyDeviceToHost);
+        bi.release(); bo.release();
+        if (e != hipSuccess) { g_err = std::string("ptrs_probe_light: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
         return PTRS_OK;
     });
 }

@@ -328,6 +328,32 @@ def selftest_div3(mode, n_sets, seed=1, device=0):
     return int(bad.value), int(fast.value), first
 
 
+def probe_bsdf(scene, material, frame, rows, device=0):
+    """ptrs_probe_bsdf: material `material` of `scene` at a hit with frame (ng, ns, dpdu), rows (n x 8: wo, wi, u) ->
+    (n x 16): f(wo, wi).rgb, pdf(wo, wi), sample_f(wo, u) f.rgb, pdf, wi.xyz, flags, has-BSDF, 0 x 3 (csrc/pt_probe.h)."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_probe_bsdf.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    fr = np.ascontiguousarray(frame, dtype=np.float32).reshape(9)
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(L.ptrs_probe_bsdf(ds.handle, int(material), C.c_void_p(fr.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def probe_light(scene, light, ref, rows, device=0):
+    """ptrs_probe_light: light `light` of `scene` (area or environment) from ref (p, n), rows (n x 5: u, w) -> (n x 16):
+    sample_li(u) wi.xyz, pdf, Li.rgb, ok; pdf_li(w); le(w).rgb; 0 x 4 (csrc/pt_probe.h)."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_probe_light.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    rf = np.ascontiguousarray(ref, dtype=np.float32).reshape(6)
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 5)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(L.ptrs_probe_light(ds.handle, int(light), C.c_void_p(rf.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def build_id():
     """ptrs_build_id: hash of the kernel sources and compiler flags the loaded library was built from (build.source_hash)."""
     return load_library().ptrs_build_id().decode()

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../pathtracer-rs_amd/csrc/pt_render.h"
+#include "../../pathtracer-rs_amd/csrc/pt_probe.h"
 
 using namespace pt;
 
@@ -214,6 +215,28 @@ int twin_sobol_samples(const PtrsRenderParams *prm, uint32_t n, const int32_t *p
         if (index_out) index_out[i] = idx;
         out[i] = sample_dimension(S, idx, dims[i], pixel_scramble(px[i], py[i]), px[i], py[i]);
     }
+    return PTRS_OK;
+}
+
+// the device probes' rows (ptrs_probe_bsdf / ptrs_probe_light) with the same argument checks
+int twin_bsdf_probe(void *sp, int32_t material, const float *frame, uint32_t n, const float *rows, float *out) {
+    TwinScene *s = static_cast<TwinScene *>(sp);
+    if (!s || !frame || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+    if (material < 0 || (size_t)material >= s->H.mats.size()) { g_err = "material index out of range"; return PTRS_ERR_INVALID; }
+    const int32_t kind = s->H.mats[material].kind;
+    if (kind < 0 || kind > 5) { g_err = "the BSDF probe takes Matte, Metal, Mirror, Glass, Disney or Substrate"; return PTRS_ERR_UNSUPPORTED; }
+    for (uint32_t i = 0; i < n; ++i) bsdf_probe_row(s->sc, material, kind, frame, rows + (size_t)i * PROBE_BSDF_IN, out + (size_t)i * PROBE_BSDF_OUT);
+    return PTRS_OK;
+}
+int twin_light_probe(void *sp, int32_t light, const float *ref, uint32_t n, const float *rows, float *out) {
+    TwinScene *s = static_cast<TwinScene *>(sp);
+    if (!s || !ref || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+    if (light < 0 || (size_t)light >= s->H.lights.size()) { g_err = "light index out of range"; return PTRS_ERR_INVALID; }
+    const int32_t kind = s->H.lights[light].kind;
+    if (kind != 2 && kind != 3) { g_err = "the light probe takes area (triangle) and environment lights"; return PTRS_ERR_UNSUPPORTED; }
+    for (uint32_t i = 0; i < n; ++i) light_probe_row(s->sc, light, ref, rows + (size_t)i * PROBE_LIGHT_IN, out + (size_t)i * PROBE_LIGHT_OUT);
     return PTRS_OK;
 }
 

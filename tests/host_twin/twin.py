@@ -76,3 +76,25 @@ def sobol_samples(params, px, py, sample_nums, dims):
     _check(lib().twin_sobol_samples(C.byref(params), px.shape[0], C.c_void_p(px.ctypes.data), C.c_void_p(py.ctypes.data), C.c_void_p(sn.ctypes.data),
                                     C.c_void_p(dm.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(idx.ctypes.data)))
     return out, idx
+
+
+def bsdf_probe(scene, material, frame, rows):
+    """twin_bsdf_probe: ptrs_probe_bsdf's rows on the CPU (scene: a TwinScene)."""
+    L = lib()
+    L.twin_bsdf_probe.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    fr = np.ascontiguousarray(frame, dtype=np.float32).reshape(9)
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(L.twin_bsdf_probe(scene._h, int(material), C.c_void_p(fr.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def light_probe(scene, light, ref, rows):
+    """twin_light_probe: ptrs_probe_light's rows on the CPU (scene: a TwinScene)."""
+    L = lib()
+    L.twin_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    rf = np.ascontiguousarray(ref, dtype=np.float32).reshape(6)
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 5)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(L.twin_light_probe(scene._h, int(light), C.c_void_p(rf.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out

@@ -87,3 +87,29 @@ def test_new_entry_points_check_their_arguments(ptrs):
     assert L.ptrs_selftest_div3(0, 0, 1, 1, None, None, None) != 0           # nowhere to put the answer
     assert ptrs.build_id() == importlib.import_module("pathtracer-rs_amd.build").source_hash()
     assert len(ptrs.build_id()) == 16
+
+
+def test_probe_entry_points_check_their_arguments(ptrs):
+    """ptrs_probe_bsdf / ptrs_probe_light (known-answer probes of csrc/pt_probe.h) refuse a missing scene, frame / reference point
+    or row buffers before they touch a device (no GPU needed)."""
+    L = ptrs.load_library()
+    L.ptrs_probe_bsdf.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.ptrs_probe_light.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    buf = (C.c_float * 64)()
+    for fn in (L.ptrs_probe_bsdf, L.ptrs_probe_light):
+        assert fn(None, 0, buf, 1, buf, buf) != 0 and b"null" in L.ptrs_last_error()     # no scene
+        assert fn(None, 0, None, 0, None, None) != 0 and b"null" in L.ptrs_last_error()   # no frame / reference point
+    import numpy as np
+    import twin
+    scene = ptrs.RenderScene()
+    m = scene.add_material(ptrs.abi.MAT_MATTE, [scene.const_rgb([0.5, 0.5, 0.5])])
+    scene.add_mesh(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.uint32), m)
+    ts = twin.TwinScene(scene)
+    # the host twin's copies of the entry points make the checks that need a scene
+    T = twin.lib()
+    T.twin_bsdf_probe.argtypes = T.twin_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    assert T.twin_bsdf_probe(ts._h, 1, buf, 1, buf, buf) != 0              # no such material
+    assert T.twin_bsdf_probe(ts._h, 0, buf, 1, None, buf) != 0             # rows missing
+    assert T.twin_bsdf_probe(ts._h, 0, buf, (1 << 24) + 1, buf, buf) != 0  # more rows than one launch takes
+    assert T.twin_light_probe(ts._h, 0, buf, 1, buf, buf) != 0             # the scene has no light
+    assert T.twin_bsdf_probe(ts._h, 0, buf, 1, buf, buf) == 0
