@@ -371,6 +371,14 @@ int ptrs_selftest_div3(int32_t device, uint32_t mode, uint64_t n_sets, uint64_t 
 #define PTRS_PROBE_MAX_ROWS (1u << 24)
 int ptrs_probe_bsdf(PtrsScene *scene, int32_t material, const float *frame, uint32_t n, const float *rows, float *out);
 int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t n, const float *rows, float *out);
+/* ptrs_probe_texture: texture `tex` of the scene (any kind) through the shade stage's tex_eval.  rows: n x 6 floats (uv.xy, dudx, dvdx,
+ * dudy, dvdy); out: n x 8 floats = rgb (1-channel textures in r), then for image textures the MIP level computed from the mapped width,
+ * 1 when the zero-footprint shortcut applies, the mapped st.xy, 0.
+ * ptrs_probe_surface: triangle `prim` of the scene (mesh order) against one ray per row, then the hit surface of the shade stage
+ * (tri_surface, surface_differentials, normal mapping for NormalMaterial wrappers).  rows: n x 16 floats (o.xyz, d.xyz, t_max,
+ * rx_d.xyz, ry_d.xyz, w.xyz); out: n x 64 floats in the layout of csrc/pt_probe.h surface_probe_row. */
+int ptrs_probe_texture(PtrsScene *scene, int32_t tex, uint32_t n, const float *rows, float *out);
+int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *rows, float *out);
 
 #ifdef __cplusplus
 }

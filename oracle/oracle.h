@@ -34,6 +34,8 @@ int orc_bsdf_eval(const PtrsMaterial *mat, const float *tex_values, uint32_t n, 
                   const float *u, float *out);
 int orc_bsdf_probe(const PtrsMaterial *mat, const float *tex_values, const float *frame, uint32_t n,
                    const float *in, float *out);
+int orc_texture_probe(OrcScene *s, int32_t tex, uint32_t n, const float *in, float *out);
+int orc_surface_probe(OrcScene *s, int32_t prim, uint32_t n, const float *in, float *out);
 #ifdef __cplusplus
 }
 #endif

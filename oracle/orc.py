@@ -84,6 +84,20 @@ class OracleScene:
         lib().orc_scene_info(self._h, C.byref(n), C.byref(d), C.byref(t))
         return dict(bvh_nodes=n.value, bvh_max_depth=d.value, n_tris=t.value)
 
+    def texture_probe(self, tex, rows):
+        """orc_texture_probe: rows (n x 6: uv, dudx, dvdx, dudy, dvdy) -> (n x 8), rgb in the layout of csrc/pt_probe.h (diagnostics 0)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((rows.shape[0], 8), dtype=np.float32)
+        _check(lib().orc_texture_probe(self._h, int(tex), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def surface_probe(self, prim, rows):
+        """orc_surface_probe: rows (n x 16: o, d, t_max, rx_d, ry_d, w) -> (n x 64) in the layout of csrc/pt_probe.h surface_probe_row."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 16)
+        out = np.zeros((rows.shape[0], 64), dtype=np.float32)
+        _check(lib().orc_surface_probe(self._h, int(prim), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+        return out
+
     def get_bvh(self):
         i = self.info()
         nodes = np.zeros(i["bvh_nodes"], dtype=np.dtype([("p_min", "<f4", 3), ("p_max", "<f4", 3), ("offset", "<u4"), ("num_prims", "<u2"), ("axis", "u1"), ("pad", "u1")]))

@@ -522,4 +522,58 @@ int orc_bsdf_probe(const PtrsMaterial *mat, const float *tex_values, const float
     return PTRS_OK;
 }
 
+// One texture of a scene per row uv, dudx, dvdx, dudy, dvdy: Texture::evaluate, in the layout of the device code's texture_probe_row
+// (rgb; the diagnostic columns stay 0).
+int orc_texture_probe(OrcScene *s, int32_t tex, uint32_t n, const float *in /* n*6 */, float *out /* n*8 */) {
+    const Scene &sc = reinterpret_cast<SceneHandle *>(s)->scene;
+    if (tex < 0 || (size_t)tex >= sc.textures.size()) { g_err = "texture index out of range"; return PTRS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = in + 6 * (size_t)i;
+        float *o = out + 8 * (size_t)i;
+        for (int k = 0; k < 8; k++) o[k] = 0.0f;
+        SurfaceInteraction si;
+        si.uv = Vec2{r[0], r[1]}; si.dudx = r[2]; si.dvdx = r[3]; si.dudy = r[4]; si.dvdy = r[5];
+        sc.textures[tex].evaluate(si, o);
+    }
+    return PTRS_OK;
+}
+
+// One triangle of a scene per row o, d, t_max, rx_d, ry_d, w: Triangle::intersect, compute_differentials (differential rays from o),
+// the NormalMaterial wrappers' normal_mapping, spawn points -- the layout of the device code's surface_probe_row (both leaf-form
+// columns hold the one answer).
+int orc_surface_probe(OrcScene *s, int32_t prim, uint32_t n, const float *in /* n*16 */, float *out /* n*64 */) {
+    const Scene &sc = reinterpret_cast<SceneHandle *>(s)->scene;
+    if (prim < 0 || (size_t)prim >= sc.tris.size()) { g_err = "triangle index out of range"; return PTRS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = in + 16 * (size_t)i;
+        float *o = out + 64 * (size_t)i;
+        for (int k = 0; k < 64; k++) o[k] = 0.0f;
+        Ray ray; ray.o = Vec3(r[0], r[1], r[2]); ray.d = Vec3(r[3], r[4], r[5]); ray.t_max = r[6];
+        float t = 0.0f;
+        SurfaceInteraction si;
+        if (!sc.tri_intersect((uint32_t)prim, ray, &t, &si, true, nullptr)) continue;
+        o[0] = o[5] = 1.0f; o[1] = o[6] = t;
+        for (int k = 0; k < 3; k++) o[2 + k] = o[7 + k] = si.bary[k];
+        RayDifferential rd(ray);
+        rd.has_differentials = true; rd.rx_origin = rd.ry_origin = ray.o;
+        rd.rx_direction = Vec3(r[7], r[8], r[9]); rd.ry_direction = Vec3(r[10], r[11], r[12]);
+        if (!si.compute_differentials(rd)) { si.dudx = si.dvdx = si.dudy = si.dvdy = 0.0f; }
+        int steps = 0;
+        for (int32_t m = sc.tris[prim].mesh < sc.meshes.size() ? sc.meshes[sc.tris[prim].mesh].material : -1;
+             steps < 4 && m >= 0 && sc.materials[m].kind == PTRS_MAT_NORMAL; ++steps) {
+            normal_mapping(sc.textures[sc.materials[m].tex[0]], si);
+            m = sc.materials[m].inner;
+        }
+        const Interaction &g = si.general;
+        const Vec3 v[8] = {g.p, g.p_error, g.n, si.shading.n, si.dpdu, si.dpdv, si.shading.dpdu, si.shading.dpdv};
+        for (int k = 0; k < 8; k++) { o[10 + 3 * k] = v[k].x; o[11 + 3 * k] = v[k].y; o[12 + 3 * k] = v[k].z; }
+        o[34] = si.uv.x; o[35] = si.uv.y; o[36] = si.dudx; o[37] = si.dvdx; o[38] = si.dudy; o[39] = si.dvdy;
+        const Vec3 w[3] = {offset_ray_origin(g.p, g.p_error, g.n, g.n), offset_ray_origin(g.p, g.p_error, g.n, Vec3(-g.n.x, -g.n.y, -g.n.z)),
+                           offset_ray_origin(g.p, g.p_error, g.n, Vec3(r[13], r[14], r[15]))};
+        for (int k = 0; k < 3; k++) { o[40 + 3 * k] = w[k].x; o[41 + 3 * k] = w[k].y; o[42 + 3 * k] = w[k].z; }
+        o[49] = (float)steps;
+    }
+    return PTRS_OK;
+}
+
 } // extern "C"

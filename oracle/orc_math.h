@@ -140,6 +140,15 @@ template <class P> inline size_t find_interval(size_t size, P pred) {
 inline int32_t round_up_pow2_i32(int32_t v) { v -= 1; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; return v + 1; }
 inline int64_t round_up_pow2_i64(int64_t v) { v -= 1; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; v |= v >> 32; return v + 1; }
 // math.rs:234-241
+// Rust `x as i32`: NaN -> 0, saturating at the ends of the range (a C++ cast is undefined there)
+inline int32_t as_i32(float x) {
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return INT32_MAX;
+    if (x < -2147483648.0f) return INT32_MIN;
+    return (int32_t)x;
+}
+// i + 1 with the wrap of the reference's release build
+inline int32_t add1_wrap(int32_t i) { return (int32_t)((uint32_t)i + 1u); }
 inline int32_t abs_mod(int32_t a, int32_t b) { int32_t r = a - (a / b) * b; return r < 0 ? r + b : r; }
 // math.rs:243-245 (usize = 64 bit)
 inline uint32_t log2_int(uint64_t i) { return 63u - (uint32_t)__builtin_clzll(i); }

@@ -115,9 +115,9 @@ struct Texture {
         float s = st.x * (float)cols[level] - 0.5f, t = st.y * (float)rows[level] - 0.5f;
         float s0f = std::floor(s), t0f = std::floor(t);
         float ds = s - s0f, dt = t - t0f;
-        int32_t s0 = (int32_t)s0f, t0 = (int32_t)t0f;
+        int32_t s0 = as_i32(s0f), t0 = as_i32(t0f); // texture.rs:422-423: `as i32` saturates
         float a[3], b[3], c[3], d[3];
-        texel(level, s0, t0, a); texel(level, s0, t0 + 1, b); texel(level, s0 + 1, t0, c); texel(level, s0 + 1, t0 + 1, d);
+        texel(level, s0, t0, a); texel(level, s0, add1_wrap(t0), b); texel(level, add1_wrap(s0), t0, c); texel(level, add1_wrap(s0), add1_wrap(t0), d);
         for (int k = 0; k < 3; k++)
             out[k] = a[k] * (1.0f - ds) * (1.0f - dt) + b[k] * (1.0f - ds) * dt + c[k] * ds * (1.0f - dt) + d[k] * ds * dt;
     }

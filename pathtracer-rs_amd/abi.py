@@ -152,7 +152,7 @@ class SceneDescHolder:
             x.normal, x.tangent, x.uv = _ptr(nrm, f32p), _ptr(tan, f32p), _ptr(uv, f32p)
             x.material = m["material"]
             x.alpha_mask_tex = m.get("alpha_mask_tex", -1)
-            x.reverse_orientation = x.transform_swaps_handedness = 0
+            x.reverse_orientation, x.transform_swaps_handedness = int(m.get("reverse_orientation", 0)), int(m.get("transform_swaps_handedness", 0))
         ls = (PtrsLight * max(len(lights), 1))()
         for i, l in enumerate(lights):
             x = ls[i]

@@ -1,4 +1,5 @@
-// pt_probe.h -- per-row probes of one material's BSDF and of one light, for known-answer tests only.
+// pt_probe.h -- per-row probes of one material's BSDF, of one light, of one texture and of one triangle's hit surface, for
+// known-answer tests only.
 //
 // The render kernels never include this file.  The gfx950 test entry points (ptrs_probe_bsdf /
 // ptrs_probe_light) and the host twin run exactly these functions, so a test can evaluate the
@@ -7,10 +8,13 @@
 // happen to go.
 #pragma once
 #include "pt_light.h"
+#include "pt_bvh.h"
+#include "pt_host_scene.h"
 
 namespace pt {
 
-enum : uint32_t { PROBE_BSDF_IN = 8, PROBE_BSDF_OUT = 16, PROBE_LIGHT_IN = 5, PROBE_LIGHT_OUT = 16 };
+enum : uint32_t { PROBE_BSDF_IN = 8, PROBE_BSDF_OUT = 16, PROBE_LIGHT_IN = 5, PROBE_LIGHT_OUT = 16, PROBE_TEX_IN = 6, PROBE_TEX_OUT = 8,
+                  PROBE_SURF_IN = 16, PROBE_SURF_OUT = 64 };
 
 // A synthetic hit for a BSDF probe: geometric normal ng, shading normal ns, shading dpdu (the
 // bsdf's ss = normalize(dpdu), ts = ns x ss: the caller passes dpdu orthogonal to ns).
@@ -74,6 +78,79 @@ PT_HD void light_probe_row(const DScene &sc, int32_t light, const float *ref /* 
     out[0] = ls.wi.x; out[1] = ls.wi.y; out[2] = ls.wi.z; out[3] = ls.pdf;
     out[4] = ls.li.x; out[5] = ls.li.y; out[6] = ls.li.z; out[7] = ok ? 1.0f : 0.0f;
     out[8] = pq; out[9] = le.x; out[10] = le.y; out[11] = le.z;
+}
+
+// Texture `tex` at one lookup.  in: uv.xy, dudx, dvdx, dudy, dvdy.  out: tex_eval<FEAT_FULL>().rgb, then for diagnosis the MIP level
+// tex_lookup_width computes from the mapped width (nl - 1 + log2(max(width, 1e-8))), 1 when its zero-footprint shortcut applies,
+// the mapped st.xy, 0.  (The diagnostic columns are 0 for constant and checker textures.)
+PT_HD void texture_probe_row(const DScene &sc, int32_t tex, const float *in, float *out) {
+    const DTexture &T = sc.texs[tex];
+    const f3 v = tex_eval<FEAT_FULL>(sc, tex, mk2(in[0], in[1]), in[2], in[3], in[4], in[5]);
+    for (uint32_t k = 0; k < PROBE_TEX_OUT; ++k) out[k] = 0.0f;
+    out[0] = v.x; out[1] = v.y; out[2] = v.z;
+    if (T.kind == 2) {
+        const float width = max_nz(max_nz(fabs_(T.su * in[2]), fabs_(T.sv * in[3])), max_nz(fabs_(T.su * in[4]), fabs_(T.sv * in[5])));
+        out[3] = (float)T.n_levels - 1.0f + pt_log2f(max_nz(width, 1e-8f));
+        out[4] = (width <= 1e-8f && T.n_levels <= 27) ? 1.0f : 0.0f;
+        out[5] = T.su * in[0] + T.du; out[6] = T.sv * in[1] + T.dv;
+    }
+}
+
+// Triangle `prim` of the scene against one ray, then the hit's surface as the shade stage builds it.
+// in: o.xyz, d.xyz, t_max, rx_d.xyz, ry_d.xyz (the differential rays leave from o, as the camera's do), w.xyz.
+// out:  0- 4 tri_test_s: hit, t, b0, b1, b2          5- 9 tri_test_s_sel: hit, t, b0, b1, b2
+//      on a hit of tri_test_s, from its b0, b1, b2 and wo = -d: tri_surface, surface_differentials, then normal_mapping for every
+//      NormalMaterial wrapper around the triangle's material (make_bsdf's order):
+//      10 p.xyz  13 p_error.xyz  16 n.xyz  19 ns.xyz  22 dpdu.xyz  25 dpdv.xyz  28 s_dpdu.xyz  31 s_dpdv.xyz  34 uv.xy
+//      36 dudx, dvdx, dudy, dvdy  40 spawn_pair(p, p_error, n).plus.xyz  43 .minus.xyz  46 offset_ray_origin(p, p_error, n, w).xyz
+//      49 number of normal_mapping steps run; the rest 0.
+PT_HD void surface_probe_row(const DScene &sc, uint32_t prim, const float *in, float *out) {
+    for (uint32_t k = 0; k < PROBE_SURF_OUT; ++k) out[k] = 0.0f;
+    const f3 o = mk3(in[0], in[1], in[2]), d = mk3(in[3], in[4], in[5]);
+    const float t_max = in[6];
+    const TriRegs T = load_tri_regs(sc.shade + prim);
+    const RayShear S = ray_shear(d);
+    TriHit h{0.0f, 0.0f, 0.0f, 0.0f}, hs{0.0f, 0.0f, 0.0f, 0.0f};
+    const bool hit = tri_test_s(o, S, t_max, T.p0, T.p1, T.p2, h);
+    const bool hit_sel = tri_test_s_sel(o, S, t_max, T.p0, T.p1, T.p2, hs);
+    out[0] = hit ? 1.0f : 0.0f;
+    if (hit) { out[1] = h.t; out[2] = h.b0; out[3] = h.b1; out[4] = h.b2; }
+    out[5] = hit_sel ? 1.0f : 0.0f;
+    if (hit_sel) { out[6] = hs.t; out[7] = hs.b0; out[8] = hs.b1; out[9] = hs.b2; }
+    if (!hit) return;
+    Surface s = tri_surface(T, (int32_t)prim, h.b0, h.b1, h.b2, -d);
+    surface_differentials(s, o, mk3(in[7], in[8], in[9]), o, mk3(in[10], in[11], in[12]));
+    const DMaterial *mp = sc.mats + T.material;
+    int steps = 0;
+    for (; steps < 4 && mp->kind == 6; ++steps) {
+        normal_mapping<FEAT_FULL>(sc, mp->tex[0], s);
+        mp = sc.mats + mp->inner;
+    }
+    const f3 v[8] = {s.p, s.p_error, s.n, s.ns, s.dpdu, s.dpdv, s.s_dpdu, s.s_dpdv};
+    for (int k = 0; k < 8; ++k) { out[10 + 3 * k] = v[k].x; out[11 + 3 * k] = v[k].y; out[12 + 3 * k] = v[k].z; }
+    out[34] = s.uv.x; out[35] = s.uv.y;
+    out[36] = s.dudx; out[37] = s.dvdx; out[38] = s.dudy; out[39] = s.dvdy;
+    const SpawnPair sp = spawn_pair(s.p, s.p_error, s.n);
+    const f3 ow = offset_ray_origin(s.p, s.p_error, s.n, mk3(in[13], in[14], in[15]));
+    const f3 w[3] = {sp.plus, sp.minus, ow};
+    for (int k = 0; k < 3; ++k) { out[40 + 3 * k] = w[k].x; out[41 + 3 * k] = w[k].y; out[42 + 3 * k] = w[k].z; }
+    out[49] = (float)steps;
+}
+
+// The argument checks of the texture / surface probes that need the scene (the device entry points and the host twin make the same
+// ones): nullptr, or why the call is refused.  A triangle's material chain (NormalMaterial wrappers, at most 4) must stay in range.
+inline const char *probe_texture_check(const HostScene &H, int32_t tex) {
+    return (tex < 0 || (size_t)tex >= H.texs.size()) ? "texture index out of range" : nullptr;
+}
+inline const char *probe_surface_check(const HostScene &H, int32_t prim) {
+    if (prim < 0 || (size_t)prim >= H.shade.size()) return "triangle index out of range";
+    int32_t m = (int32_t)f2u(reinterpret_cast<const v4 *>(&H.shade[prim])[2].y);
+    for (int k = 0; k <= 4; ++k) {
+        if (m < 0 || (size_t)m >= H.mats.size()) return "material index out of range";
+        if (H.mats[m].kind != 6 || k == 4) break;
+        m = H.mats[m].inner;
+    }
+    return nullptr;
 }
 
 } // namespace pt

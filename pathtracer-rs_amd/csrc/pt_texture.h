@@ -28,9 +28,9 @@ PT_HD f3 tex_triangle(const DScene &sc, const DTexture &T, uint32_t level, f2 st
     float s = st.x * (float)L.cols - 0.5f, t = st.y * (float)L.rows - 0.5f;
     float s0f = floor_(s), t0f = floor_(t);
     float ds = s - s0f, dt = t - t0f;
-    int32_t s0 = (int32_t)s0f, t0 = (int32_t)t0f;
-    return tex_texel(sc, T, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + tex_texel(sc, T, level, s0, t0 + 1) * (1.0f - ds) * dt +
-           tex_texel(sc, T, level, s0 + 1, t0) * ds * (1.0f - dt) + tex_texel(sc, T, level, s0 + 1, t0 + 1) * ds * dt;
+    int32_t s0 = f2i_sat(s0f), t0 = f2i_sat(t0f), s1 = inc_wrap(s0), t1 = inc_wrap(t0);
+    return tex_texel(sc, T, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + tex_texel(sc, T, level, s0, t1) * (1.0f - ds) * dt +
+           tex_texel(sc, T, level, s1, t0) * ds * (1.0f - dt) + tex_texel(sc, T, level, s1, t1) * ds * dt;
 }
 
 PT_HD f3 tex_lookup_width(const DScene &sc, const DTexture &T, f2 st, float width) {

@@ -55,6 +55,18 @@ PT_HD float max_nz(float a, float b) { return max_(a, b); }
 PT_HD float min_nz(float a, float b) { return min_(a, b); }
 #endif
 PT_HD float clamp_(float x, float lo, float hi) { if (x < lo) x = lo; if (x > hi) x = hi; return x; }
+// Rust's `x as i32` (texture.rs:422-423): NaN gives 0, values beyond the range saturate to i32::MIN / i32::MAX.  A plain C++ cast is
+// undefined there (x86-64's cvttss2si returns i32::MIN for every such value; gfx950's v_cvt_i32_f32 saturates, but the compiler may
+// assume the value in range).
+PT_HD int32_t f2i_sat(float x) {
+    if (!(x == x)) return 0;
+    if (x >= 2147483648.0f) return 2147483647;
+    if (x < -2147483648.0f) return -2147483647 - 1;
+    return (int32_t)x;
+}
+// i + 1 as the reference's release build computes it: i32::MAX + 1 wraps to i32::MIN.  (A signed `i + 1` is undefined there, and
+// hipcc then tests `i + 1 >= 0` as `i >= -1` while clamping the wrapped value: a texel index of i32::MIN, read far out of bounds.)
+PT_HD int32_t inc_wrap(int32_t i) { return (int32_t)((uint32_t)i + 1u); }
 
 struct f2 { float x, y; };
 struct f3 { float x, y, z; };

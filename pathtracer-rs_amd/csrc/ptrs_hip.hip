@@ -1289,6 +1289,17 @@ __global__ __launch_bounds__(BLOCK) void k_probe_light(DScene sc, int32_t light,
     light_probe_row(sc, light, ref.v, in + (uint64_t)i * PROBE_LIGHT_IN, out + (uint64_t)i * PROBE_LIGHT_OUT);
 }
 
+__global__ __launch_bounds__(BLOCK) void k_probe_texture(DScene sc, int32_t tex, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    texture_probe_row(sc, tex, in + (uint64_t)i * PROBE_TEX_IN, out + (uint64_t)i * PROBE_TEX_OUT);
+}
+__global__ __launch_bounds__(BLOCK) void k_probe_surface(DScene sc, uint32_t prim, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    surface_probe_row(sc, prim, in + (uint64_t)i * PROBE_SURF_IN, out + (uint64_t)i * PROBE_SURF_OUT);
+}
+
 // ---- device buffers ---------------------------------------------------------------------------------
 struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
@@ -2382,6 +2393,47 @@ int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t
         bi.release(); bo.release();
         if (e != hipSuccess) { g_err = std::string("ptrs_probe_light: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
         return PTRS_OK;
+    });
+}
+
+// (inside the C-linkage block: a template needs C++ linkage)
+extern "C++" {
+template <class Launch>
+static int probe_run(PtrsScene *scene, const char *name, uint32_t n, const float *rows, float *out, uint32_t w_in, uint32_t w_out, Launch launch) {
+    HIPCHK(hipSetDevice(scene->device));
+    if (n == 0) return PTRS_OK;
+    DevBuf bi, bo;
+    int rc;
+    if ((rc = bi.ensure((size_t)n * w_in * 4)) || (rc = bo.ensure((size_t)n * w_out * 4))) { bi.release(); bo.release(); return rc; }
+    hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * w_in * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { launch(dim3((n + BLOCK - 1) / BLOCK), (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * w_out * 4, hipMemcpyDeviceToHost);
+    bi.release(); bo.release();
+    if (e != hipSuccess) { g_err = std::string(name) + ": " + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+    return PTRS_OK;
+}
+}
+
+int ptrs_probe_texture(PtrsScene *scene, int32_t tex, uint32_t n, const float *rows, float *out) {
+    return guarded([&]() -> int {
+        if (!scene || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        if (const char *why = probe_texture_check(scene->H, tex)) { g_err = why; return PTRS_ERR_INVALID; }
+        return probe_run(scene, "ptrs_probe_texture", n, rows, out, PROBE_TEX_IN, PROBE_TEX_OUT, [&](dim3 g, const float *i, float *o) {
+            hipLaunchKernelGGL(k_probe_texture, g, dim3(BLOCK), 0, nullptr, scene->sc, tex, n, i, o);
+        });
+    });
+}
+
+int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *rows, float *out) {
+    return guarded([&]() -> int {
+        if (!scene || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        if (const char *why = probe_surface_check(scene->H, prim)) { g_err = why; return PTRS_ERR_INVALID; }
+        return probe_run(scene, "ptrs_probe_surface", n, rows, out, PROBE_SURF_IN, PROBE_SURF_OUT, [&](dim3 g, const float *i, float *o) {
+            hipLaunchKernelGGL(k_probe_surface, g, dim3(BLOCK), 0, nullptr, scene->sc, (uint32_t)prim, n, i, o);
+        });
     });
 }
 

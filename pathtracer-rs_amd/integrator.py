@@ -354,6 +354,30 @@ def probe_light(scene, light, ref, rows, device=0):
     return out
 
 
+def probe_texture(scene, tex, rows, device=0):
+    """ptrs_probe_texture: texture `tex` of `scene`, rows (n x 6: uv, dudx, dvdx, dudy, dvdy) -> (n x 8): rgb, then (image textures)
+    the MIP level computed from the width, 1 for the zero-footprint shortcut, mapped st, 0 (csrc/pt_probe.h)."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_probe_texture.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros((rows.shape[0], 8), dtype=np.float32)
+    _check(L.ptrs_probe_texture(ds.handle, int(tex), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def probe_surface(scene, prim, rows, device=0):
+    """ptrs_probe_surface: triangle `prim` of `scene`, rows (n x 16: o, d, t_max, rx_d, ry_d, w) -> (n x 64): both leaf forms' hit, t,
+    b0-b2, then the hit surface, spawn points and normal-mapping steps in the layout of csrc/pt_probe.h surface_probe_row."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_probe_surface.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 16)
+    out = np.zeros((rows.shape[0], 64), dtype=np.float32)
+    _check(L.ptrs_probe_surface(ds.handle, int(prim), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def build_id():
     """ptrs_build_id: hash of the kernel sources and compiler flags the loaded library was built from (build.source_hash)."""
     return load_library().ptrs_build_id().decode()

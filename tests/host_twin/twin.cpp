@@ -239,5 +239,21 @@ int twin_light_probe(void *sp, int32_t light, const float *ref, uint32_t n, cons
     for (uint32_t i = 0; i < n; ++i) light_probe_row(s->sc, light, ref, rows + (size_t)i * PROBE_LIGHT_IN, out + (size_t)i * PROBE_LIGHT_OUT);
     return PTRS_OK;
 }
+int twin_texture_probe(void *sp, int32_t tex, uint32_t n, const float *rows, float *out) {
+    TwinScene *s = static_cast<TwinScene *>(sp);
+    if (!s || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+    if (const char *why = probe_texture_check(s->H, tex)) { g_err = why; return PTRS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) texture_probe_row(s->sc, tex, rows + (size_t)i * PROBE_TEX_IN, out + (size_t)i * PROBE_TEX_OUT);
+    return PTRS_OK;
+}
+int twin_surface_probe(void *sp, int32_t prim, uint32_t n, const float *rows, float *out) {
+    TwinScene *s = static_cast<TwinScene *>(sp);
+    if (!s || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+    if (const char *why = probe_surface_check(s->H, prim)) { g_err = why; return PTRS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) surface_probe_row(s->sc, (uint32_t)prim, rows + (size_t)i * PROBE_SURF_IN, out + (size_t)i * PROBE_SURF_OUT);
+    return PTRS_OK;
+}
 
 } // extern "C"

@@ -98,3 +98,23 @@ def light_probe(scene, light, ref, rows):
     out = np.zeros((rows.shape[0], 16), dtype=np.float32)
     _check(L.twin_light_probe(scene._h, int(light), C.c_void_p(rf.ctypes.data), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out
+
+
+def texture_probe(scene, tex, rows):
+    """twin_texture_probe: ptrs_probe_texture's rows on the CPU (scene: a TwinScene)."""
+    L = lib()
+    L.twin_texture_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros((rows.shape[0], 8), dtype=np.float32)
+    _check(L.twin_texture_probe(scene._h, int(tex), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def surface_probe(scene, prim, rows):
+    """twin_surface_probe: ptrs_probe_surface's rows on the CPU (scene: a TwinScene)."""
+    L = lib()
+    L.twin_surface_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 16)
+    out = np.zeros((rows.shape[0], 64), dtype=np.float32)
+    _check(L.twin_surface_probe(scene._h, int(prim), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out

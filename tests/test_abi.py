@@ -113,3 +113,28 @@ def test_probe_entry_points_check_their_arguments(ptrs):
     assert T.twin_bsdf_probe(ts._h, 0, buf, (1 << 24) + 1, buf, buf) != 0  # more rows than one launch takes
     assert T.twin_light_probe(ts._h, 0, buf, 1, buf, buf) != 0             # the scene has no light
     assert T.twin_bsdf_probe(ts._h, 0, buf, 1, buf, buf) == 0
+
+
+def test_texture_and_surface_probes_check_their_arguments(ptrs):
+    """ptrs_probe_texture / ptrs_probe_surface refuse a missing scene or row buffers before they touch a device; the host twin's
+    copies make the checks that need a scene (texture / triangle index, material chain) -- no GPU needed."""
+    L = ptrs.load_library()
+    L.ptrs_probe_texture.argtypes = L.ptrs_probe_surface.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    buf = (C.c_float * 64)()
+    for fn in (L.ptrs_probe_texture, L.ptrs_probe_surface):
+        assert fn(None, 0, 1, buf, buf) != 0 and b"null" in L.ptrs_last_error()
+    import numpy as np
+    import twin
+    scene = ptrs.RenderScene()
+    m = scene.add_material(ptrs.abi.MAT_MATTE, [scene.const_rgb([0.5, 0.5, 0.5])])
+    scene.add_mesh(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.uint32), m)
+    ts = twin.TwinScene(scene)
+    T = twin.lib()
+    T.twin_texture_probe.argtypes = T.twin_surface_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    assert T.twin_texture_probe(ts._h, 1, 1, buf, buf) != 0                # no such texture
+    assert T.twin_texture_probe(ts._h, -1, 1, buf, buf) != 0
+    assert T.twin_texture_probe(ts._h, 0, 1, None, buf) != 0               # rows missing
+    assert T.twin_texture_probe(ts._h, 0, (1 << 24) + 1, buf, buf) != 0    # more rows than one launch takes
+    assert T.twin_surface_probe(ts._h, 1, 1, buf, buf) != 0                # no such triangle
+    assert T.twin_surface_probe(ts._h, 0, 1, buf, None) != 0               # out missing
+    assert T.twin_texture_probe(ts._h, 0, 1, buf, buf) == 0 and T.twin_surface_probe(ts._h, 0, 1, buf, buf) == 0
