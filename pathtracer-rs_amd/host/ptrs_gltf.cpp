@@ -862,6 +862,32 @@ bool add_infinite_light(RenderScene &s, std::vector<float> texels, int rows, int
 
 } // namespace
 
+// ---- pieces the Mitsuba importer (ptrs_host.cpp) shares with this file ----------------------------------------------
+bool load_rgb8_image(const std::string &path, int &rows, int &cols, std::vector<uint8_t> &rgb, std::string &err) {
+    std::string data; Image8 img;
+    if (!read_file(path, data)) { err = "cannot open " + path; return false; }
+    if (!decode_image(data, img, err)) return false;
+    if (!img.supported || img.ch != 3) { err = "unsupported image format for texture"; return false; } // anything but DynamicImage::ImageRgb8 (mitsuba.rs:61-63)
+    rows = img.h; cols = img.w; rgb = std::move(img.px);
+    return true;
+}
+int32_t add_spectrum_image_texture(RenderScene &s, const std::vector<uint8_t> &rgb8, int rows, int cols, int wrap, const float uvmap[4]) {
+    std::vector<float> v((size_t)rows * cols * 3); // ImageTexture::<Spectrum>::new, scale 1, gamma = true (texture.rs:123-147)
+    for (size_t k = 0; k < v.size(); ++k) v[k] = 1.0f * inverse_gamma_correct((float)rgb8[k] / 255.0f);
+    const int32_t t = add_image_texture(s, std::move(v), rows, cols, 3, wrap);
+    PtrsTexture &x = s.textures[(size_t)t]; x.su = uvmap[0]; x.sv = uvmap[1]; x.du = uvmap[2]; x.dv = uvmap[3];
+    return t;
+}
+bool add_env_light_from_file(RenderScene &s, const std::string &hdr_path, const float light_to_world[16], std::string &err) {
+    std::vector<float> rgb; int rows, cols;
+    if (!read_rgbe(hdr_path, rgb, rows, cols, err)) return false;
+    return add_infinite_light(s, std::move(rgb), rows, cols, light_to_world, err);
+}
+void matmul4(const float a[16], const float b[16], float out[16]) {
+    M4 x, y; std::memcpy(x.m, a, 64); std::memcpy(y.m, b, 64);
+    const M4 r = mul(x, y); std::memcpy(out, r.m, 64);
+}
+
 bool import_gltf(const std::string &path, int rw, int rh, bool default_lights, const std::string &env_map_path, Camera &camera, RenderScene &scene, std::string &err) {
     Importer imp;
     scene = RenderScene();

@@ -2,6 +2,7 @@
 // performs it (same order as pathtracer-rs_amd/scene.py, so both hosts emit identical bits).
 #include "ptrs_host.hpp"
 
+#include <unistd.h>
 #include <zlib.h>
 
 #include <cmath>
@@ -238,38 +239,97 @@ static int32_t add_material(RenderScene &s, int kind, std::initializer_list<int3
     s.materials.push_back(m);
     return (int32_t)s.materials.size() - 1;
 }
-static std::string snake(const std::string &s) { std::string o; for (char c : s) { if (std::isupper((unsigned char)c)) { o += '_'; o += (char)std::tolower(c); } else o += c; } return o; }
+// heck SnakeCase: a word starts at an upper-case letter after a lower-case one, and at the last letter of an upper-case run that a
+// lower-case letter follows (intIOR -> int_ior, diffuseReflectance -> diffuse_reflectance)
+static std::string snake(const std::string &s) {
+    std::string o; int mode = 0; // case of the last letter seen: 1 lower, 2 upper
+    for (size_t i = 0; i < s.size(); ++i) {
+        const unsigned char c = (unsigned char)s[i];
+        if (std::isupper(c)) {
+            const bool next_lower = i + 1 < s.size() && std::islower((unsigned char)s[i + 1]);
+            if (!o.empty() && o.back() != '_' && (mode == 1 || (mode == 2 && next_lower))) o += '_';
+            o += (char)std::tolower(c); mode = 2;
+        } else { o += (char)c; if (std::islower(c)) mode = 1; }
+    }
+    return o;
+}
+
+static bool rgb_of(const Node &n, float out[3], std::string &err) {
+    auto v = parse_floats(n.get("value"));
+    if (v.size() < 3) { err = "rgb parameter " + n.get("name") + " needs three values"; return false; }
+    out[0] = v[0]; out[1] = v[1]; out[2] = v[2];
+    return true;
+}
+
+// texture_from_mitsuba, pathtracer/importer/mitsuba.rs:24-67
+static int32_t texture_from_mitsuba(RenderScene &s, const Node &el, const std::string &base, std::string &err) {
+    const std::string kind = el.get("type");
+    if (kind == "checkerboard") {
+        std::map<std::string, const Node *> rgbs, floats;
+        for (auto &k : el.kids) { if (k->name == "rgb") rgbs[snake(k->get("name"))] = k.get(); if (k->name == "float") floats[snake(k->get("name"))] = k.get(); }
+        for (const char *name : {"color0", "color1"}) if (!rgbs.count(name)) { err = std::string("checkerboard texture without ") + name; return -1; }
+        for (const char *name : {"uscale", "vscale", "uoffset", "voffset"}) if (!floats.count(name)) { err = std::string("checkerboard texture without ") + name; return -1; }
+        PtrsTexture t{}; t.kind = PTRS_TEX_CHECKER; t.channels = 3; t.wrap = PTRS_WRAP_REPEAT;
+        if (!rgb_of(*rgbs["color0"], t.value, err) || !rgb_of(*rgbs["color1"], t.value2, err)) return -1;
+        auto f = [&](const char *name) { return std::strtof(floats[name]->get("value").c_str(), nullptr); };
+        t.su = f("uscale"); t.sv = f("vscale"); t.du = f("uoffset"); t.dv = f("voffset");
+        s.textures.push_back(t);
+        return (int32_t)s.textures.size() - 1;
+    }
+    if (kind == "bitmap") {
+        const Node *fn = el.child_named("string", "filename");
+        if (!fn) { err = "bitmap texture without filename"; return -1; }
+        int rows, cols; std::vector<uint8_t> rgb;
+        if (!load_rgb8_image(base + "/" + fn->get("value"), rows, cols, rgb, err)) return -1;
+        const float uvmap[4] = {1.0f, -1.0f, 0.0f, 0.0f}; // the reference's own TODO: "verify that this -1 on the v is actually a feature of mitsuba"
+        return add_spectrum_image_texture(s, rgb, rows, cols, PTRS_WRAP_REPEAT, uvmap);
+    }
+    err = "unsupported texture type " + kind;
+    return -1;
+}
 
 // material_from_bsdf, pathtracer/importer/mitsuba.rs:84-181
-static int32_t material_from_bsdf(RenderScene &s, const Node &el, std::string &err) {
+static int32_t material_from_bsdf(RenderScene &s, const Node &el, const std::string &base, std::string &err) {
     const std::string kind = el.get("type");
     std::map<std::string, std::vector<float>> rgbs; std::map<std::string, float> floats;
     for (auto &k : el.kids) {
-        if (k->name == "rgb") rgbs[k->get("name")] = parse_floats(k->get("value"));
+        if (k->name == "rgb") { float c[3]; if (!rgb_of(*k, c, err)) return -1; rgbs[k->get("name")] = {c[0], c[1], c[2]}; }
         if (k->name == "float") floats[snake(k->get("name"))] = std::strtof(k->get("value").c_str(), nullptr);
     }
-    auto rgb = [&](const char *a, const char *b) -> std::vector<float> { if (rgbs.count(a)) return rgbs[a]; if (b && rgbs.count(b)) return rgbs[b]; return {1.0f, 1.0f, 1.0f}; };
-    if (kind == "twosided") { const Node *in = el.child("bsdf"); if (!in) { err = "twosided without bsdf"; return -1; } return material_from_bsdf(s, *in, err); }
-    if (kind == "diffuse") { auto c = rgb("reflectance", nullptr); return add_material(s, PTRS_MAT_MATTE, {add_const_tex(s, 3, c[0], c[1], c[2])}); }
+    const Node *texture = el.child("texture");
+    // texture_with_defaults (mitsuba.rs:69-82): texture, else rgb, else 1
+    auto with_defaults = [&](const char *a, const char *b) -> int32_t {
+        if (texture) return texture_from_mitsuba(s, *texture, base, err);
+        std::vector<float> c = {1.0f, 1.0f, 1.0f};
+        if (rgbs.count(a)) c = rgbs[a]; else if (b && rgbs.count(b)) c = rgbs[b];
+        return add_const_tex(s, 3, c[0], c[1], c[2]);
+    };
+    if (kind == "twosided") { const Node *in = el.child("bsdf"); if (!in) { err = "twosided without bsdf"; return -1; } return material_from_bsdf(s, *in, base, err); }
+    if (kind == "diffuse") { int32_t t0 = with_defaults("reflectance", nullptr); if (t0 < 0) return -1; return add_material(s, PTRS_MAT_MATTE, {t0}); }
     if (kind == "conductor" || kind == "roughconductor") {
         const Node *mat = el.child_named("string", "material");
         if (kind == "conductor" && mat) { if (mat->get("value") == "none") return add_material(s, PTRS_MAT_MIRROR, {}); err = "other material values not supported yet!"; return -1; }
         if (!rgbs.count("eta") || !rgbs.count("k")) { err = "conductor without eta/k"; return -1; }
-        auto e = rgbs["eta"], k = rgbs["k"], r = rgb("specularReflectance", "specular_reflectance");
+        if (kind == "roughconductor" && !floats.count("alpha")) { err = "roughconductor without alpha"; return -1; }
+        auto e = rgbs["eta"], k = rgbs["k"];
         float alpha = kind == "conductor" ? 0.001f : floats["alpha"];
-        int32_t t0 = add_const_tex(s, 3, e[0], e[1], e[2]), t1 = add_const_tex(s, 3, k[0], k[1], k[2]), t2 = add_const_tex(s, 3, r[0], r[1], r[2]), t3 = add_const_tex(s, 1, alpha, 0, 0);
+        int32_t t0 = add_const_tex(s, 3, e[0], e[1], e[2]), t1 = add_const_tex(s, 3, k[0], k[1], k[2]);
+        int32_t t2 = with_defaults("specularReflectance", "specular_reflectance"); if (t2 < 0) return -1;
+        int32_t t3 = add_const_tex(s, 1, alpha, 0, 0);
         return add_material(s, PTRS_MAT_METAL, {t0, t1, t2, t3, -1, -1}, 0);
     }
     if (kind == "dielectric") {
+        if (!floats.count("int_ior")) { err = "dielectric without intIOR"; return -1; }
         int32_t t0 = add_const_tex(s, 3, 1, 1, 1), t1 = add_const_tex(s, 3, 1, 1, 1), t2 = add_const_tex(s, 1, floats["int_ior"], 0, 0);
         return add_material(s, PTRS_MAT_GLASS, {t0, t1, t2});
     }
     if (kind == "plastic" || kind == "roughplastic") {
+        if (!floats.count("int_ior") || (kind == "roughplastic" && !floats.count("alpha"))) { err = kind + " without intIOR / alpha"; return -1; }
         float e = floats["int_ior"];
         float r0 = ((e - 1.0f) * (e - 1.0f)) / ((e + 1.0f) * (e + 1.0f));
         float a = kind == "plastic" ? 0.001f : floats["alpha"];
-        auto kd = rgb("diffuseReflectance", "diffuse_reflectance");
-        int32_t t0 = add_const_tex(s, 3, kd[0], kd[1], kd[2]), t1 = add_const_tex(s, 3, r0, r0, r0), t2 = add_const_tex(s, 1, a, 0, 0), t3 = add_const_tex(s, 1, a, 0, 0);
+        int32_t t0 = with_defaults("diffuseReflectance", "diffuse_reflectance"); if (t0 < 0) return -1;
+        int32_t t1 = add_const_tex(s, 3, r0, r0, r0), t2 = add_const_tex(s, 1, a, 0, 0), t3 = add_const_tex(s, 1, a, 0, 0);
         return add_material(s, PTRS_MAT_SUBSTRATE, {t0, t1, t2, t3}, 0);
     }
     err = "unsupported bsdf type " + kind;
@@ -295,6 +355,99 @@ static void gen_cube(std::vector<float> &pos, std::vector<float> &nrm, std::vect
         uint32_t b = 4u * f;
         idx.insert(idx.end(), {b, b + 1, b + 2, b, b + 2, b + 3});
     }
+}
+
+// genmesh 0.6.2 SphereUv::new(10, 10) under Similarity3(center, no rotation, radius) (common/importer/mitsuba.rs:60-79; restated from
+// memory): pole, 9 rings of 10, pole; 10 triangles, 80 quads as (x,y,z),(x,z,w), 10 triangles.  The normal is the unit vertex.
+static void gen_sphere(const float center[3], float radius, std::vector<float> &pos, std::vector<float> &nrm, std::vector<uint32_t> &idx) {
+    const int su = 10, sv = 10;
+    const float PI = 3.14159274101257324f;
+    pos.clear(); nrm.clear(); idx.clear();
+    auto vert = [&](int u, int v) {
+        const float a = ((float)u / (float)su) * PI * 2.0f, b = ((float)v / (float)sv) * PI;
+        const float ca = (float)std::cos((double)a), sa = (float)std::sin((double)a), cb = (float)std::cos((double)b), sb = (float)std::sin((double)b);
+        const float n[3] = {ca * sb, sa * sb, cb};
+        for (int c = 0; c < 3; ++c) { nrm.push_back(n[c]); pos.push_back(n[c] * radius + center[c]); }
+    };
+    vert(0, 0);
+    for (int v = 1; v < sv; ++v) for (int u = 0; u < su; ++u) vert(u, v);
+    vert(0, sv);
+    auto f = [&](int u, int v) -> uint32_t { return v == 0 ? 0u : v == sv ? (uint32_t)((sv - 1) * su + 1) : (uint32_t)((v - 1) * su + (u % su) + 1); };
+    for (int v = 0; v < sv; ++v) for (int u = 0; u < su; ++u) {
+        if (v == 0) idx.insert(idx.end(), {f(u, v), f(u, v + 1), f(u + 1, v + 1)});
+        else if (v == sv - 1) idx.insert(idx.end(), {f(u + 1, v + 1), f(u + 1, v), f(u, v)});
+        else { const uint32_t x = f(u, v), y = f(u, v + 1), z = f(u + 1, v + 1), w = f(u + 1, v); idx.insert(idx.end(), {x, y, z, x, z, w}); }
+    }
+}
+
+// load_obj (common/importer/mitsuba.rs:81-151): the v / vn / vt lists in file order and the triangles; one object, one geometry,
+// triangles only, normals required, position = normal = texture index at every corner.  Values are parsed as binary64 and narrowed.
+static bool load_obj(const std::string &path, std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &uv, std::vector<uint32_t> &idx, std::string &err) {
+    std::ifstream f(path);
+    if (!f) { err = "cannot open " + path; return false; }
+    auto fail = [&](const std::string &rule) { err = path + ": " + rule; return false; };
+    pos.clear(); nrm.clear(); uv.clear(); idx.clear();
+    std::vector<long> raw;
+    int n_obj = 0, n_mtl = 0;
+    std::string line;
+    while (std::getline(f, line)) {
+        const std::string body = line.substr(0, line.find('#'));
+        std::istringstream is(body); std::vector<std::string> tok; std::string t;
+        while (is >> t) tok.push_back(t);
+        if (tok.empty()) continue;
+        const std::string &key = tok[0]; const size_t na = tok.size() - 1;
+        auto malformed = [&]() { size_t a = line.find_first_not_of(" \t\r\n"), b = line.find_last_not_of(" \t\r\n"); return fail("malformed line: " + (a == std::string::npos ? std::string() : line.substr(a, b - a + 1))); };
+        auto floats = [&](size_t n, std::vector<float> &out) { for (size_t k = 1; k <= n; ++k) { char *e; const double v = std::strtod(tok[k].c_str(), &e); if (e == tok[k].c_str() || *e) return false; out.push_back((float)v); } return true; };
+        if (key == "v") { if (na < 3) return fail("v needs three coordinates"); if (!floats(3, pos)) return malformed(); }
+        else if (key == "vn") { if (na < 3) return fail("vn needs three coordinates"); if (!floats(3, nrm)) return malformed(); }
+        else if (key == "vt") { if (na < 2) return fail("vt needs two coordinates"); if (!floats(2, uv)) return malformed(); }
+        else if (key == "f") {
+            if (na != 3) return fail("only triangle faces are supported");
+            for (size_t k = 1; k <= 3; ++k) {
+                std::vector<std::string> parts; size_t a = 0;
+                for (;;) { const size_t b = tok[k].find('/', a); parts.push_back(tok[k].substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
+                long v[3] = {0, 0, 0}; bool have[3] = {false, false, false};
+                for (size_t c = 0; c < parts.size() && c < 3; ++c) { if (parts[c].empty()) { if (c == 0) return malformed(); continue; } char *e; v[c] = std::strtol(parts[c].c_str(), &e, 10); if (*e) return malformed(); have[c] = true; }
+                if (!have[2]) return fail("faces need normals (v/vt/vn or v//vn)");
+                if (v[0] != v[2]) return fail("position and normal index must be equal");
+                if (have[1] && v[0] != v[1]) return fail("position and texture index must be equal");
+                raw.push_back(v[0] > 0 ? v[0] : (long)(pos.size() / 3) + 1 + v[0]);
+            }
+        }
+        else if (key == "o") { if (++n_obj > 1) return fail("only one object is supported"); }
+        else if (key == "usemtl") { if (++n_mtl > 1) return fail("only one geometry (usemtl) per object is supported"); }
+        else if (key == "g" || key == "s" || key == "mtllib") {}
+        else return fail("unsupported statement " + key);
+    }
+    if (raw.empty()) return fail("no faces");
+    if (nrm.size() != pos.size()) return fail("normal count must equal vertex count");
+    if (!uv.empty() && uv.size() / 2 != pos.size() / 3) return fail("texture coordinate count must equal vertex count");
+    for (long v : raw) { if (v < 1 || v > (long)(pos.size() / 3)) return fail("face index out of range"); idx.push_back((uint32_t)(v - 1)); }
+    return true;
+}
+
+// Matrix4::from_euler_angles(-pi/2, -pi/2, 0).append_nonuniform_scaling((1, 1, -1)) (pathtracer/importer/mitsuba.rs:365-372):
+// Rz(yaw) Ry(pitch) Rx(roll) written out as nalgebra does, then the ROWS scaled.  [[0,1,0],[0,0,1],[-1,0,0]] for exact angles.
+static void env_light_to_world(float m[16]) {
+    const float h = (float)(-3.14159265358979323846 / 2.0); // -f32::consts::FRAC_PI_2
+    const float sr = (float)std::sin((double)h), cr = (float)std::cos((double)h), sp = sr, cp = cr, sy = 0.0f, cy = 1.0f;
+    const float e[16] = {cy * cp, (cy * sp) * sr - sy * cr, (cy * sp) * cr + sy * sr, 0,
+                         sy * cp, (sy * sp) * sr + cy * cr, (sy * sp) * cr - cy * sr, 0,
+                         -sp, cp * sr, cp * cr, 0, 0, 0, 0, 1};
+    const float sc[3] = {1.0f, 1.0f, -1.0f};
+    std::memcpy(m, e, 64);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m[4 * r + c] = m[4 * r + c] * sc[r];
+}
+
+static std::string default_env_map_path() { // the reference reads it from its source tree (CARGO_MANIFEST_DIR/data)
+    const char *name = "data/abandoned_tank_farm_04_1k.hdr";
+    char buf[4096]; const ssize_t n = readlink("/proc/self/exe", buf, sizeof(buf) - 1);
+    if (n > 0) {
+        std::string exe(buf, (size_t)n); const size_t k = exe.find_last_of('/');
+        const std::string p = (k == std::string::npos ? std::string(".") : exe.substr(0, k)) + "/../" + name;
+        if (std::ifstream(p)) return p;
+    }
+    return name;
 }
 
 // get_camera (common/importer/mitsuba.rs:685-710, Q30) + Camera::new (common/mod.rs:33-62)
@@ -369,30 +522,65 @@ bool import_scene(const std::string &path, int res_w, int res_h, Camera &camera,
     if (cm.size() != 16) { err = "camera matrix needs 16 values"; return false; }
     make_camera(cm.data(), std::strtof(fovn->get("value").c_str(), nullptr), std::atoi(fw->get("value").c_str()), std::atoi(fh->get("value").c_str()), res_w, res_h, camera);
     scene = RenderScene();
+    const size_t slash = path.find_last_of('/');
+    const std::string base = slash == std::string::npos ? "." : path.substr(0, slash);
     std::map<std::string, int32_t> named;
-    for (auto &k : root->kids) if (k->name == "bsdf") { int32_t m = material_from_bsdf(scene, *k, err); if (m < 0) return false; named[k->get("id")] = m; }
+    for (auto &k : root->kids) if (k->name == "bsdf") { int32_t m = material_from_bsdf(scene, *k, base, err); if (m < 0) return false; named[k->get("id")] = m; }
     for (auto &k : root->kids) {
         if (k->name != "shape") continue;
-        std::vector<float> pos, nrm; std::vector<uint32_t> idx;
+        std::vector<float> pos, nrm, uv; std::vector<uint32_t> idx;
         const std::string kind = k->get("type");
-        if (kind == "rectangle") gen_rectangle(pos, nrm, idx);
-        else if (kind == "cube") gen_cube(pos, nrm, idx);
-        else { err = "unsupported shape type " + kind; return false; }
         float M[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
         if (const Node *t = k->child("transform")) if (const Node *mn = t->child("matrix")) { auto v = parse_floats(mn->get("value")); if (v.size() != 16) { err = "shape matrix needs 16 values"; return false; } std::memcpy(M, v.data(), 64); }
-        Mesh mesh; mesh.pos.resize(pos.size()); mesh.normal.resize(nrm.size()); mesh.indices = idx;
-        for (size_t v = 0; v < pos.size() / 3; ++v) { transform_point(M, &pos[3 * v], &mesh.pos[3 * v]); transform_vector(M, &nrm[3 * v], &mesh.normal[3 * v]); } // Q15
+        if (kind == "rectangle") gen_rectangle(pos, nrm, idx);
+        else if (kind == "cube") gen_cube(pos, nrm, idx);
+        else if (kind == "sphere") {
+            const Node *pt = k->child("point"), *rad = k->child("float");
+            if (!pt || !rad) { err = "sphere needs a center point and a radius"; return false; }
+            const float c[3] = {std::strtof(pt->get("x").c_str(), nullptr), std::strtof(pt->get("y").c_str(), nullptr), std::strtof(pt->get("z").c_str(), nullptr)};
+            gen_sphere(c, std::strtof(rad->get("value").c_str(), nullptr), pos, nrm, idx);
+            const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            std::memcpy(M, I, 64); // Shape::Sphere has no transform: obj_to_world stays the identity
+        } else if (kind == "obj") {
+            const Node *fn = k->child("string");
+            if (!fn) { err = "obj shape without filename"; return false; }
+            if (!load_obj(base + "/" + fn->get("value"), pos, nrm, uv, idx, err)) return false;
+            if (const Node *b = k->child("boolean")) if (b->get("value") == "true") { std::fprintf(stderr, "WARN face normals on for obj, vertex normals will be disregarded\n"); nrm.clear(); }
+        } else { err = "unsupported shape type " + kind; return false; }
+        Mesh mesh; mesh.pos.resize(pos.size()); mesh.normal.resize(nrm.size()); mesh.uv = uv; mesh.indices = idx;
+        for (size_t v = 0; v < pos.size() / 3; ++v) transform_point(M, &pos[3 * v], &mesh.pos[3 * v]);
+        for (size_t v = 0; v < nrm.size() / 3; ++v) transform_vector(M, &nrm[3 * v], &mesh.normal[3 * v]); // Q15
         if (const Node *ref = k->child("ref")) { auto it = named.find(ref->get("id")); if (it == named.end()) { err = "unknown bsdf id " + ref->get("id"); return false; } mesh.material = it->second; }
-        else if (const Node *b = k->child("bsdf")) { mesh.material = material_from_bsdf(scene, *b, err); if (mesh.material < 0) return false; }
+        else if (const Node *b = k->child("bsdf")) { mesh.material = material_from_bsdf(scene, *b, base, err); if (mesh.material < 0) return false; }
         else { err = "either ref exists or embedded bsdf exists"; return false; }
         const uint32_t mi = (uint32_t)scene.meshes.size();
         if (const Node *em = k->child("emitter")) if (em->get("type") == "area") { // one DiffuseAreaLight per triangle (mitsuba.rs:306-323)
             const Node *rad = em->child("rgb");
-            auto c = parse_floats(rad ? rad->get("value") : "1 1 1");
+            float c[3] = {1, 1, 1};
+            if (rad && !rgb_of(*rad, c, err)) return false;
             int32_t ke = add_const_tex(scene, 3, c[0], c[1], c[2]);
             for (uint32_t t = 0; t < idx.size() / 3; ++t) { PtrsLight L{}; L.kind = PTRS_LIGHT_AREA; L.mesh = mi; L.tri = t; L.ke_tex = ke; L.lmap_tex = -1; scene.lights.push_back(L); }
         }
         scene.meshes.push_back(std::move(mesh));
+    }
+    // scene-level emitters join the list after every shape's area lights, in document order (mitsuba.rs:374-420)
+    for (auto &k : root->kids) {
+        if (k->name != "emitter") continue;
+        const std::string kind = k->get("type");
+        float E[16]; env_light_to_world(E);
+        if (kind == "area") std::fprintf(stderr, "WARN area lights should not be standalone!\n");
+        else if (kind == "point") {}
+        else if (kind == "envmap") {
+            const Node *fn = k->child("string"), *t = k->child("transform"), *mn = t ? t->child("matrix") : nullptr;
+            if (!fn || !mn) { err = "envmap emitter needs a toWorld matrix and a filename"; return false; }
+            auto v = parse_floats(mn->get("value"));
+            if (v.size() != 16) { err = "envmap matrix needs 16 values"; return false; }
+            float L2W[16]; matmul4(v.data(), E, L2W);
+            if (!add_env_light_from_file(scene, base + "/" + fn->get("value"), L2W, err)) return false;
+        } else if (kind == "sunsky") {
+            std::fprintf(stderr, "WARN sunsky emitter not supported, putting default env map instead\n");
+            if (!add_env_light_from_file(scene, env_map_path.empty() ? default_env_map_path() : env_map_path, E, err)) return false;
+        } else { err = "unsupported emitter type " + kind; return false; }
     }
     return true;
 }

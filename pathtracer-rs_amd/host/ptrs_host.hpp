@@ -7,7 +7,7 @@
 //   from_gltf / RenderScene::from_gltf                  src/common/importer/gltf.rs, src/pathtracer/importer/gltf.rs (ptrs_gltf.cpp)
 //   Camera::new / get_camera                            src/common/mod.rs:33-62, importer/mitsuba.rs:685-710
 //   Film::{new, clear, get_sample_bounds, to_rgba_image} src/common/film.rs:132-251
-//   RenderScene::from_mitsuba                           src/pathtracer/importer/mitsuba.rs:84-428 (rgb-parameter subset)
+//   RenderScene::from_mitsuba                           src/pathtracer/importer/mitsuba.rs:24-428, common/importer/mitsuba.rs:20-151
 //   SamplerBuilder::new                                 src/pathtracer/sampler/sobol.rs:35-60
 //   PathIntegrator::{new, preprocess, render}           src/pathtracer/integrator.rs:230,250,536
 // The Python package (pathtracer-rs_amd/*.py) mirrors the same surface for tests and bench.py; both
@@ -124,9 +124,11 @@ private:
 // (ptrs_render_row_cost: a few milliseconds).  Returns false and fills err on failure.
 bool probe_row_cost(PtrsScene *scene, const PtrsCamera &camera, const PtrsRenderParams &params, int strips, std::vector<float> &row_cost, std::string &err);
 
-// importer::import for Mitsuba XML (rectangle / cube shapes, twosided / diffuse / conductor /
-// roughconductor / dielectric / plastic / roughplastic bsdfs with rgb parameters, area emitters,
-// perspective sensor).  Returns false and fills err on failure.
+// importer::import for Mitsuba XML (rectangle / cube / sphere / obj shapes, twosided / diffuse / conductor /
+// roughconductor / dielectric / plastic / roughplastic bsdfs with rgb or checkerboard / bitmap texture parameters,
+// area emitters on shapes, envmap / sunsky emitters, perspective sensor).  Returns false and fills err on failure.
+// A sunsky emitter falls back to data/abandoned_tank_farm_04_1k.hdr, looked for next to the executable's directory
+// (../data) and under the working directory, unless env_map_path names another Radiance file.
 bool import_scene(const std::string &path, int res_w, int res_h, Camera &camera, RenderScene &scene, std::string &err,
                   bool default_lights = false, const std::string &env_map_path = "");
 // the .gltf / .glb branch (ptrs_gltf.cpp).  default_lights adds the environment light of `--default_lights`; the
@@ -135,6 +137,14 @@ bool import_gltf(const std::string &path, int res_w, int res_h, bool default_lig
                  Camera &camera, RenderScene &scene, std::string &err);
 // Camera::new (common/mod.rs:33-62) from an isometry (unit quaternion i,j,k,w + translation) and Perspective3::new arguments
 void make_camera_perspective(const float rot_ijkw[4], const float trans[3], float aspect, float fovy, float znear, float zfar, int res_w, int res_h, Camera &cam);
+
+// Pieces of ptrs_gltf.cpp that the Mitsuba importer uses as well: an RGB8 image file (PNG / baseline JPEG; any other pixel format is
+// "unsupported image format for texture"), ImageTexture::<Spectrum>::new(image, 1, wrap, UVMap(uvmap), gamma = true) with its MIP
+// pyramid, InfiniteAreaLight::new from a Radiance file, and the 4x4 binary32 product in the order both hosts use.
+bool load_rgb8_image(const std::string &path, int &rows, int &cols, std::vector<uint8_t> &rgb, std::string &err);
+int32_t add_spectrum_image_texture(RenderScene &scene, const std::vector<uint8_t> &rgb8, int rows, int cols, int wrap, const float uvmap[4]);
+bool add_env_light_from_file(RenderScene &scene, const std::string &hdr_path, const float light_to_world[16], std::string &err);
+void matmul4(const float a[16], const float b[16], float out[16]);
 
 bool write_png_rgba8(const std::string &path, int w, int h, const std::vector<uint8_t> &rgba, std::string &err);
 bool dump_scene(const std::string &path, const Camera &camera, const RenderScene &scene);

@@ -2,19 +2,21 @@
 
 Mirrors (reference file:line, relative to /root/reference):
   * common/importer/mod.rs:6-25            import(path, resolution)           -> import_scene
-  * common/importer/mitsuba.rs:20-79       gen_rectangle / gen_cube (genmesh 0.6.2 Plane/Cube)
+  * common/importer/mitsuba.rs:20-151      gen_rectangle / gen_cube / gen_sphere (genmesh 0.6.2 Plane/Cube/SphereUv), load_obj
   * common/importer/mitsuba.rs:685-710     get_camera
   * common/mod.rs:33-62                    Camera::new
-  * pathtracer/importer/mitsuba.rs:84-428  material_from_bsdf / parse_shape / RenderScene::from_mitsuba
+  * pathtracer/importer/mitsuba.rs:24-428  texture_from_mitsuba / material_from_bsdf / parse_shape / RenderScene::from_mitsuba
   * common/film.rs:132-185                 Film (resolution, sample bounds)
-Only the Mitsuba subset needed by data/cornell-box.xml and simple test scenes is parsed
-(rectangle, cube, twosided/diffuse/conductor/roughconductor/dielectric/plastic bsdfs with rgb
-parameters, area emitters, perspective sensor).  Everything here is host-side set-up that the
+Every Mitsuba construct the reference's importer accepts is parsed: rectangle / cube / sphere / obj
+shapes, twosided / diffuse / conductor / roughconductor / dielectric / plastic / roughplastic bsdfs
+with rgb or texture (checkerboard, bitmap) parameters, area emitters on shapes, envmap / sunsky
+emitters, the perspective sensor.  Everything here is host-side set-up that the
 reference also does once, outside PathIntegrator::render; the results cross the C ABI as flat
 arrays (include/ptrs.h).  All arithmetic is binary32 in the order nalgebra 0.32.2 performs it.
 """
 import math
 import os
+import warnings
 import xml.etree.ElementTree as ET
 
 import numpy as np
@@ -70,6 +72,124 @@ def gen_cube():
         b = 4 * f
         indices += [[b, b + 1, b + 2], [b, b + 2, b + 3]]
     return np.array(pos, dtype=np.float32), np.array(normal, dtype=np.float32), np.array(indices, dtype=np.uint32)
+
+
+def gen_sphere(center, radius):
+    """SphereUv::new(10, 10) under Similarity3(center, no rotation, radius)  (common/importer/mitsuba.rs:60-79):
+    92 shared vertices (pole, 9 rings of 10, pole), unit vertex (cos a sin b, sin a sin b, cos b) with
+    a = u/10 * pi * 2, b = v/10 * pi in binary32; 100 polygons (10 triangles, 80 quads, 10 triangles), quads
+    triangulated as (x,y,z),(x,z,w).  The normal is the unit vertex: the similarity is not applied to it."""
+    su = sv = 10
+    pi = F(math.pi)
+
+    def vert(u, v):
+        a = (F(u) / F(su)) * pi * F(2.0)
+        b = (F(v) / F(sv)) * pi
+        ca, sa = F(math.cos(float(a))), F(math.sin(float(a)))
+        cb, sb = F(math.cos(float(b))), F(math.sin(float(b)))
+        return [ca * sb, sa * sb, cb]
+
+    unit = [vert(0, 0)] + [vert(u, v) for v in range(1, sv) for u in range(su)] + [vert(0, sv)]
+
+    def f(u, v):
+        if v == 0:
+            return 0
+        if v == sv:
+            return (sv - 1) * su + 1
+        return (v - 1) * su + (u % su) + 1
+
+    indices = []
+    for v in range(sv):
+        for u in range(su):
+            if v == 0:
+                indices.append([f(u, v), f(u, v + 1), f(u + 1, v + 1)])
+            elif v == sv - 1:
+                indices.append([f(u + 1, v + 1), f(u + 1, v), f(u, v)])
+            else:
+                x, y, z, w = f(u, v), f(u, v + 1), f(u + 1, v + 1), f(u + 1, v)
+                indices += [[x, y, z], [x, z, w]]
+    normal = np.array(unit, dtype=np.float32)
+    c, r = np.array(center, dtype=np.float32), F(radius)
+    pos = (normal * r + c).astype(np.float32)  # Similarity3 * Point: scale, (identity rotation), translate
+    return pos, normal, np.array(indices, dtype=np.uint32)
+
+
+def load_obj(path):
+    """load_obj (common/importer/mitsuba.rs:81-151): the file's v / vn / vt lists in file order and its triangles.
+    One object, one geometry, triangles only, normals required, and at every corner the position, normal and
+    texture index are equal.  The values are parsed as binary64 and narrowed, as the reference does."""
+    pos, normal, uv, indices = [], [], [], []
+    n_obj = n_mtl = 0
+
+    def fail(rule):
+        raise ValueError("%s: %s" % (path, rule))
+
+    try:
+        text = open(path, "r").read()
+    except OSError:
+        raise ValueError("cannot open " + str(path))
+    for line in text.splitlines():
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        key, args = tok[0], tok[1:]
+        try:
+            if key == "v":
+                if len(args) < 3:
+                    fail("v needs three coordinates")
+                pos.append([F(float(a)) for a in args[:3]])
+            elif key == "vn":
+                if len(args) < 3:
+                    fail("vn needs three coordinates")
+                normal.append([F(float(a)) for a in args[:3]])
+            elif key == "vt":
+                if len(args) < 2:
+                    fail("vt needs two coordinates")
+                uv.append([F(float(a)) for a in args[:2]])
+            elif key == "f":
+                if len(args) != 3:
+                    fail("only triangle faces are supported")
+                tri = []
+                for a in args:
+                    parts = a.split("/")
+                    p = int(parts[0])
+                    t = int(parts[1]) if len(parts) > 1 and parts[1] else None
+                    n = int(parts[2]) if len(parts) > 2 and parts[2] else None
+                    if n is None:
+                        fail("faces need normals (v/vt/vn or v//vn)")
+                    if p != n:
+                        fail("position and normal index must be equal")
+                    if t is not None and p != t:
+                        fail("position and texture index must be equal")
+                    tri.append(p if p > 0 else len(pos) + 1 + p)
+                indices.append(tri)
+            elif key == "o":
+                n_obj += 1
+                if n_obj > 1:
+                    fail("only one object is supported")
+            elif key == "usemtl":
+                n_mtl += 1
+                if n_mtl > 1:
+                    fail("only one geometry (usemtl) per object is supported")
+            elif key in ("g", "s", "mtllib"):
+                pass
+            else:
+                fail("unsupported statement " + key)
+        except ValueError as e:
+            if str(e).startswith(str(path)):
+                raise
+            fail("malformed line: " + line.strip())
+    if not indices:
+        fail("no faces")
+    if len(normal) != len(pos):
+        fail("normal count must equal vertex count")
+    if uv and len(uv) != len(pos):
+        fail("texture coordinate count must equal vertex count")
+    idx = np.array(indices, dtype=np.int64)
+    if idx.min() < 1 or idx.max() > len(pos):
+        fail("face index out of range")
+    return (np.array(pos, dtype=np.float32), np.array(normal, dtype=np.float32),
+            np.array(uv, dtype=np.float32) if uv else None, (idx - 1).astype(np.uint32))
 
 
 # ---- camera ---------------------------------------------------------------------------------------
@@ -278,45 +398,158 @@ def _parse_matrix(el):
     return _mat4([float(v) for v in el.get("value").split()])
 
 
-def _bsdf_to_material(scene, el):
-    """material_from_bsdf, pathtracer/importer/mitsuba.rs:84-181 (rgb-parameter subset)."""
+def _snake(name):
+    """heck SnakeCase: a word starts at an upper-case letter after a lower-case one, and at the last letter of an
+    upper-case run that a lower-case letter follows (intIOR -> int_ior, diffuseReflectance -> diffuse_reflectance)."""
+    out, mode = [], 0  # mode: case of the last letter seen, 1 lower, 2 upper
+    for i, ch in enumerate(name):
+        if ch.isupper():
+            nxt = name[i + 1] if i + 1 < len(name) else ""
+            if out and out[-1] != "_" and (mode == 1 or (mode == 2 and nxt.islower())):
+                out.append("_")
+            out.append(ch.lower())
+            mode = 2
+        else:
+            out.append(ch)
+            if ch.islower():
+                mode = 1
+    return "".join(out)
+
+
+def _rgb_value(el):
+    v = [float(x) for x in el.get("value", "").replace(",", " ").split()]
+    if len(v) < 3:
+        raise ValueError("rgb parameter %s needs three values" % el.get("name"))
+    return v[:3]
+
+
+def _texture_from_mitsuba(scene, el, base):
+    """texture_from_mitsuba, pathtracer/importer/mitsuba.rs:24-67."""
     kind = el.get("type")
-    rgbs = {c.get("name"): [float(v) for v in c.get("value").replace(",", " ").split()] for c in el.findall("rgb")}
-    floats = {c.get("name"): float(c.get("value")) for c in el.findall("float")}
-    floats = {"".join("_" + ch.lower() if ch.isupper() else ch for ch in k): v for k, v in floats.items()}  # heck SnakeCase
+    if kind == "checkerboard":
+        rgbs = {_snake(c.get("name")): _rgb_value(c) for c in el.findall("rgb")}
+        floats = {_snake(c.get("name")): float(c.get("value")) for c in el.findall("float")}
+        for name, have in (("color0", rgbs), ("color1", rgbs), ("uscale", floats), ("vscale", floats), ("uoffset", floats), ("voffset", floats)):
+            if name not in have:
+                raise ValueError("checkerboard texture without " + name)
+        return scene.add_texture(kind=abi.TEX_CHECKER, channels=3, value=np.array(rgbs["color0"], dtype=np.float32), value2=np.array(rgbs["color1"], dtype=np.float32),
+                                 su=floats["uscale"], sv=floats["vscale"], du=floats["uoffset"], dv=floats["voffset"], wrap=abi.WRAP_REPEAT, levels=[])
+    if kind == "bitmap":
+        from PIL import Image
+        from . import textures as tx
+        fn = el.find("string[@name='filename']")
+        if fn is None:
+            raise ValueError("bitmap texture without filename")
+        path = os.path.join(base, fn.get("value"))
+        try:
+            img = Image.open(path)
+            img.load()
+        except OSError:
+            raise ValueError("cannot open " + path)
+        if img.mode == "P" and "transparency" not in img.info:
+            img = img.convert("RGB")
+        if img.mode != "RGB":
+            raise ValueError("unsupported image format for texture")
+        # TODO in the reference: "verify that this -1 on the v is actually a feature of mitsuba"
+        return tx.spectrum_texture(scene, np.array(img, dtype=np.uint8), wrap=abi.WRAP_REPEAT, uvmap=(1.0, -1.0, 0.0, 0.0), gamma=True)
+    raise ValueError("unsupported texture type " + str(kind))
+
+
+def _bsdf_to_material(scene, el, base="."):
+    """material_from_bsdf, pathtracer/importer/mitsuba.rs:84-181."""
+    kind = el.get("type")
+    rgbs = {c.get("name"): _rgb_value(c) for c in el.findall("rgb")}
+    floats = {_snake(c.get("name")): float(c.get("value")) for c in el.findall("float")}
+    texture = el.find("texture")
+
+    def with_defaults(rgb):  # texture_with_defaults: texture, else rgb, else 1
+        if texture is not None:
+            return _texture_from_mitsuba(scene, texture, base)
+        return scene.const_rgb(rgb if rgb is not None else [1, 1, 1])
+
     if kind == "twosided":
-        return _bsdf_to_material(scene, el.find("bsdf"))
+        if el.find("bsdf") is None:
+            raise ValueError("twosided without bsdf")
+        return _bsdf_to_material(scene, el.find("bsdf"), base)
     if kind == "diffuse":
-        return scene.add_material(abi.MAT_MATTE, [scene.const_rgb(rgbs.get("reflectance", [1, 1, 1]))])
+        return scene.add_material(abi.MAT_MATTE, [with_defaults(rgbs.get("reflectance"))])
     if kind in ("conductor", "roughconductor"):
         mat = el.find("string[@name='material']")
         if kind == "conductor" and mat is not None:
             if mat.get("value") == "none":
                 return scene.add_material(abi.MAT_MIRROR)
             raise ValueError("other material values not supported yet!")
-        r = rgbs.get("specularReflectance", rgbs.get("specular_reflectance", [1, 1, 1]))
+        if "eta" not in rgbs or "k" not in rgbs:
+            raise ValueError("conductor without eta/k")
+        if kind == "roughconductor" and "alpha" not in floats:
+            raise ValueError("roughconductor without alpha")
         alpha = 0.001 if kind == "conductor" else floats["alpha"]
-        return scene.add_material(abi.MAT_METAL, [scene.const_rgb(rgbs["eta"]), scene.const_rgb(rgbs["k"]), scene.const_rgb(r), scene.const_f(alpha), -1, -1], flags=0)
+        eta, k = scene.const_rgb(rgbs["eta"]), scene.const_rgb(rgbs["k"])
+        r = with_defaults(rgbs.get("specularReflectance", rgbs.get("specular_reflectance")))
+        return scene.add_material(abi.MAT_METAL, [eta, k, r, scene.const_f(alpha), -1, -1], flags=0)
     if kind == "dielectric":
+        if "int_ior" not in floats:
+            raise ValueError("dielectric without intIOR")
         return scene.add_material(abi.MAT_GLASS, [scene.const_rgb([1, 1, 1]), scene.const_rgb([1, 1, 1]), scene.const_f(floats["int_ior"])])
     if kind in ("plastic", "roughplastic"):
+        if "int_ior" not in floats or (kind == "roughplastic" and "alpha" not in floats):
+            raise ValueError(kind + " without intIOR / alpha")
         e = F(floats["int_ior"])
         r0 = ((e - F(1)) * (e - F(1))) / ((e + F(1)) * (e + F(1)))
         a = 0.001 if kind == "plastic" else floats["alpha"]
-        kd = rgbs.get("diffuseReflectance", rgbs.get("diffuse_reflectance", [1, 1, 1]))
-        return scene.add_material(abi.MAT_SUBSTRATE, [scene.const_rgb(kd), scene.const_rgb([r0] * 3), scene.const_f(a), scene.const_f(a)], flags=0)
+        kd = with_defaults(rgbs.get("diffuseReflectance", rgbs.get("diffuse_reflectance")))
+        return scene.add_material(abi.MAT_SUBSTRATE, [kd, scene.const_rgb([r0] * 3), scene.const_f(a), scene.const_f(a)], flags=0)
     raise ValueError("unsupported bsdf type " + str(kind))
+
+
+def matmul4(a, b):
+    """4x4 product in binary32, inner index ascending from the first product (the order both hosts use)."""
+    r = np.zeros((4, 4), dtype=np.float32)
+    for i in range(4):
+        for j in range(4):
+            acc = a[i, 0] * b[0, j]
+            for k in range(1, 4):
+                acc = acc + a[i, k] * b[k, j]
+            r[i, j] = acc
+    return r
+
+
+def env_light_to_world():
+    """Matrix4::from_euler_angles(-pi/2, -pi/2, 0).append_nonuniform_scaling((1, 1, -1))
+    (pathtracer/importer/mitsuba.rs:365-372): Rz(yaw) Ry(pitch) Rx(roll) written out as nalgebra does, then the
+    ROWS scaled.  For exact angles this is [[0,1,0],[0,0,1],[-1,0,0]]."""
+    h = F(-math.pi / 2)  # -f32::consts::FRAC_PI_2
+    sr, cr = F(math.sin(float(h))), F(math.cos(float(h)))
+    sp, cp = sr, cr
+    sy, cy = F(0.0), F(1.0)
+    m = np.eye(4, dtype=np.float32)
+    m[0, :3] = [cy * cp, (cy * sp) * sr - sy * cr, (cy * sp) * cr + sy * sr]
+    m[1, :3] = [sy * cp, (sy * sp) * sr + cy * cr, (sy * sp) * cr - cy * sr]
+    m[2, :3] = [-sp, cp * sr, cp * cr]
+    for r, f in enumerate((F(1.0), F(1.0), F(-1.0))):
+        m[r, :] = m[r, :] * f
+    return m
+
+
+DEFAULT_ENV_MAP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "abandoned_tank_farm_04_1k.hdr")
+
+
+def _shape_matrix(sh):
+    el = sh.find("transform/matrix")
+    return _parse_matrix(el) if el is not None else np.eye(4, dtype=np.float32)
 
 
 def import_scene(path, resolution, default_lights=False, env_map=None):
     """common/importer/mod.rs:6-25: dispatch on the extension; returns (Camera, RenderScene).
-    .gltf / .glb -> gltf.import_gltf (default_lights = the CLI's --default_lights); .xml -> the Mitsuba subset."""
+    .gltf / .glb -> gltf.import_gltf (default_lights = the CLI's --default_lights); .xml -> Mitsuba.  For a Mitsuba
+    scene `env_map` names the Radiance file a sunsky emitter falls back to (default: the bundled data/ map)."""
     ext = os.path.splitext(str(path))[1].lower()
     if ext in (".gltf", ".glb"):
         from .gltf import import_gltf
         return import_gltf(path, resolution, default_lights=default_lights, env_map=env_map)
     if ext != ".xml":
         raise ValueError("unsupported format!")
+    base = os.path.dirname(str(path)) or "."
     root = ET.parse(path).getroot()
     sensor = root.find("sensor")
     fov = float(sensor.find("float[@name='fov']").get("value"))
@@ -327,23 +560,70 @@ def import_scene(path, resolution, default_lights=False, env_map=None):
     scene = RenderScene()
     named = {}
     for b in root.findall("bsdf"):
-        named[b.get("id")] = _bsdf_to_material(scene, b)
+        named[b.get("id")] = _bsdf_to_material(scene, b, base)
     for sh in root.findall("shape"):
         kind = sh.get("type")
+        uv = None
+        m = _shape_matrix(sh)
         if kind == "rectangle":
             pos, normal, indices = gen_rectangle()
         elif kind == "cube":
             pos, normal, indices = gen_cube()
+        elif kind == "sphere":
+            pt, rad = sh.find("point"), sh.find("float")
+            if pt is None or rad is None:
+                raise ValueError("sphere needs a center point and a radius")
+            pos, normal, indices = gen_sphere([float(pt.get(a, "0")) for a in "xyz"], float(rad.get("value")))
+            m = np.eye(4, dtype=np.float32)  # Shape::Sphere has no transform: obj_to_world stays the identity
+        elif kind == "obj":
+            fn = sh.find("string")
+            if fn is None:
+                raise ValueError("obj shape without filename")
+            pos, normal, uv, indices = load_obj(os.path.join(base, fn.get("value")))
+            fnrm = sh.find("boolean")
+            if fnrm is not None and fnrm.get("value") == "true":
+                warnings.warn("face normals on for obj, vertex normals will be disregarded")
+                normal = None
         else:
-            raise ValueError("unsupported shape type " + kind)
-        m = _parse_matrix(sh.find("transform/matrix")) if sh.find("transform/matrix") is not None else np.eye(4, dtype=np.float32)
+            raise ValueError("unsupported shape type " + str(kind))
         wpos = np.array([transform_point(m, p) for p in pos], dtype=np.float32)
-        wnrm = np.array([transform_vector(m, n) for n in normal], dtype=np.float32)  # Q15: forward matrix, no renormalise
+        wnrm = np.array([transform_vector(m, n) for n in normal], dtype=np.float32) if normal is not None else None  # Q15: forward matrix, no renormalise
         ref = sh.find("ref")
-        mat = named[ref.get("id")] if ref is not None else _bsdf_to_material(scene, sh.find("bsdf"))
+        if ref is not None:
+            if ref.get("id") not in named:
+                raise ValueError("unknown bsdf id " + str(ref.get("id")))
+            mat = named[ref.get("id")]
+        elif sh.find("bsdf") is not None:
+            mat = _bsdf_to_material(scene, sh.find("bsdf"), base)
+        else:
+            raise ValueError("either ref exists or embedded bsdf exists")
         em = sh.find("emitter")
         emission = None
         if em is not None and em.get("type") == "area":
-            emission = [float(v) for v in em.find("rgb").get("value").replace(",", " ").split()]
-        scene.add_mesh(wpos, indices, mat, normal=wnrm, emission_rgb=emission)
+            emission = _rgb_value(em.find("rgb")) if em.find("rgb") is not None else [1.0, 1.0, 1.0]
+        scene.add_mesh(wpos, indices, mat, normal=wnrm, uv=uv, emission_rgb=emission)
+    # scene-level emitters join the list after every shape's area lights, in document order (mitsuba.rs:374-420)
+    for em in root.findall("emitter"):
+        kind = em.get("type")
+        if kind == "area":
+            warnings.warn("area lights should not be standalone!")
+        elif kind == "point":
+            pass
+        elif kind == "envmap":
+            from . import textures as tx
+            fn, mt = em.find("string"), em.find("transform/matrix")
+            if fn is None or mt is None:
+                raise ValueError("envmap emitter needs a toWorld matrix and a filename")
+            hdr = os.path.join(base, fn.get("value"))
+            if not os.path.exists(hdr):
+                raise ValueError("cannot open " + hdr)
+            tx.add_infinite_light(scene, tx.read_rgbe(hdr), light_to_world=matmul4(_parse_matrix(mt), env_light_to_world()))
+        elif kind == "sunsky":
+            from . import textures as tx
+            warnings.warn("sunsky emitter not supported, putting default env map instead")
+            hdr = env_map if env_map is not None else DEFAULT_ENV_MAP
+            img = tx.read_rgbe(hdr) if isinstance(hdr, (str, os.PathLike)) else np.asarray(hdr, dtype=np.float32)
+            tx.add_infinite_light(scene, img, light_to_world=env_light_to_world())
+        else:
+            raise ValueError("unsupported emitter type " + str(kind))
     return cam, scene
