@@ -256,4 +256,21 @@ int twin_surface_probe(void *sp, int32_t prim, uint32_t n, const float *rows, fl
     return PTRS_OK;
 }
 
+// pt::camera_ray once per row: p_film (n x 2) -> o, d, rx_d, ry_d (n x 12).  The render kernels reach the same function through
+// generate_item and shade_item; this entry hands its rays out for the float64 comparison of tests/test_camera_film_kat.py.
+int twin_camera_rays(const PtrsCamera *cam, float diff_scale, uint32_t n, const float *pfilm, float *out) {
+    if (!cam || (n && (!pfilm || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    DCamera C;
+    std::memcpy(C.rot, cam->rot, 16); std::memcpy(C.trans, cam->trans, 12);
+    C.m00 = cam->m00; C.m11 = cam->m11; C.m22 = cam->m22; C.m23 = cam->m23;
+    std::memcpy(C.r2s, cam->raster_to_screen, 64); std::memcpy(C.dxc, cam->dx_camera, 12); std::memcpy(C.dyc, cam->dy_camera, 12);
+    for (uint32_t i = 0; i < n; ++i) {
+        const CamRay r = camera_ray(C, mk2(pfilm[2 * (size_t)i], pfilm[2 * (size_t)i + 1]), diff_scale);
+        float *o = out + (size_t)i * 12;
+        o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
+        o[6] = r.rx_d.x; o[7] = r.rx_d.y; o[8] = r.rx_d.z; o[9] = r.ry_d.x; o[10] = r.ry_d.y; o[11] = r.ry_d.z;
+    }
+    return PTRS_OK;
+}
+
 } // extern "C"

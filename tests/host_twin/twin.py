@@ -118,3 +118,14 @@ def surface_probe(scene, prim, rows):
     out = np.zeros((rows.shape[0], 64), dtype=np.float32)
     _check(L.twin_surface_probe(scene._h, int(prim), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out
+
+
+def camera_rays(camera, diff_scale, pfilm):
+    """twin_camera_rays: pt::camera_ray for every p_film row (n x 2) -> (n x 12): o, d, rx_d, ry_d."""
+    L = lib()
+    L.twin_camera_rays.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+    cam = camera.to_abi()
+    pf = np.ascontiguousarray(pfilm, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros((pf.shape[0], 12), dtype=np.float32)
+    _check(L.twin_camera_rays(C.byref(cam), float(diff_scale), pf.shape[0], C.c_void_p(pf.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
