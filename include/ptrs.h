@@ -315,6 +315,23 @@ int ptrs_render_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRen
 int ptrs_render_samples(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params,
                         PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats);
 
+/* First-hit feature planes for a denoiser or a compositor (no counterpart in the reference): albedo, shading normal and depth +
+ * coverage of the camera samples of `params`' render, filtered onto the film by exactly the samples and weights of the beauty image
+ * (same sampler, sample grid, row bands and pass plan; max_depth is ignored: the pass ends behind its first extension, and a specular
+ * first hit is not followed).  planes: which planes to gather (plane k = bit k); planes_inout[k]: that plane's film, ACCUMULATED like
+ * ptrs_render's -- rgb = sums of albedo | shading normal | (depth, coverage, 0) times the filter weight, weight = the filter-weight sum.
+ * Albedo is the base colour slot of the innermost material (Matte kd, Metal r, Glass kr, Disney color, Substrate kd; Mirror and an
+ * absent slot: 1, 1, 1); a sample that misses contributes zeros.  sample_aov: NULL, or 12 floats per sample laid out like
+ * ptrs_render_samples' sample_rgb: albedo.rgb, coverage, normal.xyz, depth, position.xyz, the triangle id's bit pattern (0xffffffff:
+ * miss); samples outside the call's sample rows stay 0.  The _device form takes the planes (and sample_aov) in device memory and a stream. */
+enum { PTRS_AOV_ALBEDO = 1u, PTRS_AOV_NORMAL = 2u, PTRS_AOV_DEPTH = 4u };
+#define PTRS_AOV_PLANES 3
+#define PTRS_AOV_SAMPLE_FLOATS 12
+int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes,
+                    PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats);
+int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes,
+                           void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats);
+
 /* PathIntegrator::render_single_pixel (integrator.rs:505-534): radiance of every sample of one
  * pixel, rgb_out[spp*3]. */
 int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera,

@@ -14,6 +14,10 @@ MAT_MATTE, MAT_METAL, MAT_MIRROR, MAT_GLASS, MAT_DISNEY, MAT_SUBSTRATE, MAT_NORM
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_AREA, LIGHT_INFINITE = range(4)
 FLAG_COUNTERS, FLAG_TIMING, FLAG_FILM_ZERO = 1, 2, 4
 SAMPLER_SOBOL, SAMPLER_STRATIFIED = 0, 1
+# ptrs_render_aov: plane k = bit k; floats per sample of its per-sample export
+PtrsAovAlbedo, PtrsAovNormal, PtrsAovDepth = 1, 2, 4
+PtrsAovPlanes, PtrsAovSampleFloats = 3, 12
+PtrsAovNames = ("albedo", "normal", "depth")
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)

@@ -1,0 +1,221 @@
+// pt_aov.h -- first-hit feature planes (albedo, shading normal, depth + coverage) on the camera samples.
+//
+// A denoiser or a compositor wants, next to the radiance film, what the camera rays saw: filtered onto the film by exactly the samples
+// and weights of the beauty image.  Everything that is needed sits in the pipeline after round 0 -- the hit (triangle id, barycentrics)
+// in P.hit, the film position in P.pfilm -- so an AOV call is a render cut after its first extension: generate, extend(0), then
+//   aov_item          : camera_ray -> tri_surface -> surface_differentials -> the NormalMaterial chain (make_bsdf's order) -> the values
+//   render_aov_impl   : render_impl's sample grid, sampler, row bands, pass plan and lanes around those three stages and the plane films
+// Specular first hits are not followed: a mirror shows the mirror's own surface.  The reference has no such call.
+#pragma once
+#include "pt_render.h"
+
+namespace pt {
+
+enum : uint32_t { AOV_ALBEDO = 0, AOV_NORMAL = 1, AOV_DEPTH = 2, AOV_PLANES = 3, AOV_SAMPLE_FLOATS = 12 };
+
+// What k_aov leaves per path slot, in path-state arrays an AOV pass has no other use for (max_depth 0: no vertex is shaded, nothing
+// is connected).  depthp (the depth plane as the film gathers it: depth, coverage, 0) is written only for the per-plane film launches.
+struct DAov {
+    v4 *albedo; // [pid]: albedo.rgb, coverage
+    v4 *normal; // [pid]: shading normal (world space), depth
+    v4 *pos;    // [pid]: hit position, the triangle id's bits
+    v4 *depthp; // [pid] or null: depth, coverage, 0, 0
+    f2a *pfilm; // [pid] or null: a copy of p_film beside the values (band mode of render_aov_impl: the arrays outlive the pass)
+};
+struct DAovFilm { v4 *plane[AOV_PLANES]; }; // film of plane k (device memory, W x H), null when the plane is not asked for
+
+struct AovRec { f3 albedo; float coverage; f3 normal; float depth; f3 p; uint32_t prim; };
+
+// The texture slot that holds a material kind's base colour; -1: the kind has none (Mirror reflects everything: 1, 1, 1).
+PT_HD int aov_albedo_slot(int32_t kind) {
+    switch (kind) {
+        case PTRS_MAT_MATTE: case PTRS_MAT_GLASS: case PTRS_MAT_DISNEY: case PTRS_MAT_SUBSTRATE: return 0; // kd, kr, color, kd
+        case PTRS_MAT_METAL: return 2;                                                                    // r
+        default: return -1;
+    }
+}
+
+// The planes' values of one camera sample: p_film and the hit word of round 0 (P.hit: packed triangle id, barycentrics).
+template <int FEAT>
+PT_HD AovRec aov_item(const DParams &R, const DCamera &C, const DScene &sc, f2 pf, u4 hit) {
+    AovRec a;
+    a.albedo = a.normal = a.p = splat3(0.0f); a.coverage = 0.0f; a.depth = 0.0f; a.prim = 0xffffffffu;
+    const int32_t prim = hit_prim(hit.x);
+    if (prim < 0) return a;
+    const CamRay cr = camera_ray(C, pf, R.inv_sqrt_spp);
+    const TriRegs T = load_tri_regs(sc.shade + prim);
+    Surface s = tri_surface(T, prim, u2f(hit.y), u2f(hit.z), u2f(hit.w), -cr.d);
+    surface_differentials(s, cr.o, cr.rx_d, cr.o, cr.ry_d);
+    const DMaterial *mp = sc.mats + T.material;
+    if (FEAT & FEAT_NORMAL) {
+        for (int guard = 0; guard < 4 && mp->kind == PTRS_MAT_NORMAL; ++guard) {
+            normal_mapping<FEAT>(sc, mp->tex[0], s);
+            mp = sc.mats + mp->inner;
+        }
+    }
+    const DMaterial &m = *mp;
+    const int slot = aov_albedo_slot(m.kind);
+    a.albedo = (slot >= 0 && m.tex[slot] >= 0) ? mat_tex<FEAT>(sc, m, slot, s) : splat3(1.0f);
+    a.coverage = 1.0f;
+    a.normal = s.ns;
+    a.p = s.p;
+    a.depth = len(s.p - cr.o);
+    a.prim = (uint32_t)prim;
+    return a;
+}
+
+// One sample's 12 floats of ptrs_render_aov's sample_aov: albedo, coverage, normal, depth, position, triangle id bits
+PT_HD void aov_sample_row(const AovRec &a, float *o) {
+    o[0] = a.albedo.x; o[1] = a.albedo.y; o[2] = a.albedo.z; o[3] = a.coverage;
+    o[4] = a.normal.x; o[5] = a.normal.y; o[6] = a.normal.z; o[7] = a.depth;
+    o[8] = a.p.x; o[9] = a.p.y; o[10] = a.p.z; o[11] = u2f(a.prim);
+}
+
+// The AOV call: render_impl's argument checks, sample grid, sampler set-up, row bands, pass plan and lanes (the same plan: a plane's
+// weight channel is then formed by the very additions of the beauty film's) with max_depth forced to 0, and per pass
+//     pass_begin -> generate -> extend(0) -> aov -> the plane films, chained in pass order.
+// The survival profile of the scene (be.learn / be.tail_round) belongs to beauty renders and is neither read nor fed.
+// A plan that cuts the band's ROWS into blocks (a band of one sample exceeds the pass capacity: then every pass holds one sample index)
+// would hand a pixel at a block boundary its samples block by block, where a plan of whole-band passes hands them over sample by
+// sample: other float32 sums.  The planes must not depend on the pass size, so such a plan runs in BAND MODE: the same passes, ordered
+// sample index first, leave their values (and p_film) in arrays of the whole band (72 bytes per sample pixel), and when a sample
+// index's last block is through ONE film gather runs over the band -- the order of a whole-band pass: sample, x, y.  On one lane: the
+// stream orders the blocks, the gather and the next sample's blocks.
+template <class BE>
+int render_aov_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm_in,
+                    uint32_t planes, const DAovFilm &films /* backend memory, W*H each */, float *samples_out /* backend memory or null */, PtrsStats *stats, std::string &err) {
+    using clock = std::chrono::steady_clock;
+    auto t_begin = clock::now();
+    if (prm_in.width <= 0 || prm_in.height <= 0 || prm_in.spp <= 0 || prm_in.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (bvh_depth > 64) { err = "BVH deeper than the 64-entry traversal stack (accelerator.rs:370)"; return PTRS_ERR_UNSUPPORTED; }
+    PtrsRenderParams prm = prm_in;
+    prm.max_depth = 0; // the pass ends behind its first extension: the epilogue buckets nothing
+    SampleGrid g = make_sample_grid(prm.width, prm.height, prm.spp);
+    uint32_t strat_dim = 0;
+    if (prm.sampler == PTRS_SAMPLER_STRATIFIED) {
+        strat_dim = 1; while ((strat_dim + 1u) * (strat_dim + 1u) <= (uint32_t)prm.spp) ++strat_dim;
+        if (strat_dim * strat_dim != (uint32_t)prm.spp) { err = "stratified sampler: spp must be dim_pixel_samples squared"; return PTRS_ERR_INVALID; }
+        if (prm.n_sampled_dimensions < 3 * (prm.max_depth + 1) + 1 || prm.n_sampled_dimensions > 63) { err = "stratified sampler: n_sampled_dimensions must be 4 .. 63"; return PTRS_ERR_UNSUPPORTED; }
+        g.spp = strat_dim * strat_dim;
+    } else if (prm.sampler != PTRS_SAMPLER_SOBOL) { err = "unknown sampler"; return PTRS_ERR_INVALID; }
+    if (g.log2_res < 1 || g.log2_res > 25 || 2u * g.log2_res + (31u - (uint32_t)__builtin_clz(g.spp)) > 62u) { err = "resolution / spp outside the Sobol index range"; return PTRS_ERR_UNSUPPORTED; }
+    int32_t rb = prm.row_begin, re = prm.row_end;
+    if (re <= rb) { rb = 0; re = prm.height; }
+    if (rb < 0 || re > prm.height) { err = "row band outside the film"; return PTRS_ERR_INVALID; }
+    const int32_t srow0 = std::max(rb, 0), srow1 = std::min(re + 4, g.NY); // sample rows (grid coordinates) whose footprint can touch output rows [rb, re)
+
+    DSampler S;
+    S.matrices = be.sobol_matrices(); S.bytetab = be.sobol_bytetab(); S.nibtab = be.sobol_nibtab(); S.vdc = be.sobol_vdc(g.log2_res - 1); S.vdc_inv = be.sobol_vdc_inv(g.log2_res - 1);
+    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
+    S.kind = (uint32_t)prm.sampler; S.strat_dims = (uint32_t)prm.n_sampled_dimensions; S.strat1 = nullptr; S.strat2 = nullptr;
+    if (strat_dim) {
+        int rc_t = be.strat_tables(g.NX, g.NY, strat_dim, S.strat_dims, &S.strat1, &S.strat2, err);
+        if (rc_t != PTRS_OK) return rc_t;
+    }
+    DCamera C;
+    std::memcpy(C.rot, cam.rot, 16); std::memcpy(C.trans, cam.trans, 12);
+    C.m00 = cam.m00; C.m11 = cam.m11; C.m22 = cam.m22; C.m23 = cam.m23;
+    std::memcpy(C.r2s, cam.raster_to_screen, 64); std::memcpy(C.dxc, cam.dx_camera, 12); std::memcpy(C.dyc, cam.dy_camera, 12);
+    DParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.max_depth = 0; R.rr_threshold = prm.rr_threshold; R.rr_start_depth = prm.rr_start_depth; R.rr_enable = prm.rr_enable;
+    R.NX = g.NX; R.NY = g.NY; R.W = prm.width; R.H = prm.height;
+    R.inv_sqrt_spp = 1.0f / std::sqrt((float)g.spp);
+    R.counters_on = (prm.flags & PTRS_FLAG_COUNTERS) ? 1u : 0u;
+
+    // ---- pass planning: render_impl's, line for line ------------------------------------------
+    const uint32_t n_lanes = std::max(1u, be.lanes((uint64_t)(srow1 - srow0) * (uint64_t)g.NX * (uint64_t)g.spp, sc_host_feat.kinds_present, false, g.spp));
+    uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, sc_host_feat.kinds_present));
+    if (capacity < (uint64_t)g.NX) capacity = (uint64_t)g.NX;
+    const uint64_t band_rows = (uint64_t)(srow1 - srow0);
+    uint64_t rows_per_pass, samples_per_pass;
+    if (band_rows * (uint64_t)g.NX <= capacity) {
+        rows_per_pass = band_rows;
+        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
+        const uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
+        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
+    } else {
+        samples_per_pass = 1;
+        const uint64_t rows_max = std::max<uint64_t>(1, capacity / (uint64_t)g.NX);
+        const uint64_t n_chunks = (band_rows + rows_max - 1) / rows_max;
+        rows_per_pass = (band_rows + n_chunks - 1) / n_chunks;
+    }
+    if (n_lanes > 1 && band_rows * (uint64_t)g.NX <= capacity && !prm.paths_per_pass) {
+        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
+        uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
+        if (g.spp >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes;
+        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
+    }
+    const uint64_t max_paths = rows_per_pass * (uint64_t)g.NX * samples_per_pass;
+    if (max_paths >= 0xffffffffull) { err = "pass too large"; return PTRS_ERR_INVALID; }
+
+    const uint32_t count_rows = 2u; // round 0, and the row its kernels may look ahead to
+    const int feat = scene_features(sc_host_feat), feat_trace = scene_trace_features(sc_host_feat);
+    int rc = be.begin(sc, S, C, (uint32_t)max_paths, count_rows, bvh_depth, prm.flags, feat, feat_trace, err);
+    if (rc != PTRS_OK) return rc;
+
+    PtrsStats st;
+    std::memset(&st, 0, sizeof(st));
+    std::vector<uint32_t> counts((size_t)count_rows * Q_STRIDE);
+    const bool band_mode = rows_per_pass < band_rows; // (samples_per_pass == 1)
+    if (band_mode) {
+        if (band_rows * (uint64_t)g.NX > (1ull << 27)) { err = "band too large for the pass capacity"; return PTRS_ERR_UNSUPPORTED; }
+        if ((rc = be.aov_band_begin(band_rows * (uint64_t)g.NX, err)) != PTRS_OK) return rc;
+    }
+    struct Pass { int32_t r0, r1; uint32_t s0, s1; bool last_block; };
+    std::vector<Pass> plan;
+    if (band_mode) {
+        for (uint32_t s0 = 0; s0 < g.spp; ++s0)
+            for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass) plan.push_back(Pass{r0, std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass), s0, s0 + 1u, r0 + (int32_t)rows_per_pass >= srow1});
+    } else {
+        for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass)
+            for (uint32_t s0 = 0; s0 < g.spp; s0 += (uint32_t)samples_per_pass) plan.push_back(Pass{r0, std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass), s0, (uint32_t)std::min<uint64_t>(g.spp, (uint64_t)s0 + samples_per_pass), true});
+    }
+    struct Pending { bool active = false; uint32_t n_paths = 0; };
+    std::vector<Pending> pending(n_lanes);
+    auto finish = [&](uint32_t lane) { // the counters of the pass a lane ran last (waits for that lane only)
+        Pending &pd = pending[lane];
+        if (!pd.active) return;
+        be.select(lane);
+        be.read_counts(counts.data(), 1u);
+        st.rays_extension += counts[Q_EXT];
+        st.rays_shadow += counts[Q_SHADOW];
+        st.rays_mis += counts[Q_MIS];
+        st.samples += pd.n_paths;
+        st.passes += 1;
+        pd.active = false;
+    };
+    uint32_t pass_no = 0;
+    for (const Pass &ps : plan) {
+        const uint32_t lane = band_mode ? 0u : pass_no % n_lanes;
+        finish(lane);
+        be.select(lane);
+        R.row0 = ps.r0; R.row1 = ps.r1; R.s0 = ps.s0; R.s1 = ps.s1;
+        R.n_paths = (uint32_t)(ps.r1 - ps.r0) * (uint32_t)g.NX * (ps.s1 - ps.s0);
+        const uint32_t off = band_mode ? (uint32_t)(ps.r0 - srow0) * (uint32_t)g.NX : 0u; // the pass's first slot in the band's arrays
+        be.pass_begin(R);
+        be.generate();
+        be.extend(0);
+        be.aov(planes, off);
+        if (samples_out) be.export_aov(samples_out, off);
+        // output rows touched by the sample rows gathered: pixel row = min_y + sample row, +-2
+        const int32_t f0 = band_mode ? srow0 : ps.r0, f1 = band_mode ? srow1 : ps.r1;
+        const int32_t y0 = std::max(rb, g.min_y + f0 - 2), y1 = std::min(re, g.min_y + f1 - 1 + 2 + 1);
+        if (ps.last_block && y1 > y0) { // ordered after the previous film launches, whichever lane ran them
+            DParams Rf = R;
+            if (band_mode) { Rf.row0 = srow0; Rf.row1 = srow1; Rf.n_paths = (uint32_t)band_rows * (uint32_t)g.NX; }
+            be.film_aov(planes, films, y0, y1, Rf);
+        }
+        pending[lane].active = true; pending[lane].n_paths = R.n_paths;
+        ++pass_no;
+    }
+    st.ms_enqueue = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();
+    for (uint32_t k = 0; k < n_lanes; ++k) finish((pass_no + k) % n_lanes);
+    be.end(st);
+    st.bvh_nodes = sc.n_nodes; st.bvh_max_depth = bvh_depth;
+    st.ms_total = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();
+    if (stats) *stats = st;
+    return PTRS_OK;
+}
+
+} // namespace pt

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pt_render.h"
+#include "pt_aov.h"
 #include "pt_probe.h"
 
 using namespace pt;
@@ -61,6 +62,7 @@ struct Options {
     int tail_at = -1;         // the round at which a pass hands over to k_tail: -1 = the first round in which the paths expected alive (this scene's survival profile, learned from its last finished pass) are at most tail_paths per segment; k >= 0: round k
     int tail_paths = 0;       // (tail_at = -1) paths per segment at or below which the tail takes over; 0 = the measured default (TAIL_PATHS_DEFAULT)
     int workspace_pct = 40;   // the render workspace (path state + queues of all lanes) may take this share of the device memory that is free at the call
+    int aov_fused_film = 1;   // ptrs_render_aov: the planes' films are gathered by ONE k_film_aov launch per pass; 0: one k_film launch per plane (same bits)
 };
 Options g_opt;
 std::mutex g_opt_mu;
@@ -68,7 +70,7 @@ Options options() { std::lock_guard<std::mutex> lk(g_opt_mu); return g_opt; }
 struct OptionDesc { const char *name; int Options::*field; int lo, hi; };
 const OptionDesc k_options[] = {
     {"lanes", &Options::lanes, 0, 8}, {"refill", &Options::refill, -1, 64}, {"refill_connect", &Options::refill_connect, -1, 64}, {"stack_lds", &Options::stack_lds, 8, 16},
-    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20},
+    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20}, {"aov_fused_film", &Options::aov_fused_film, 0, 1},
 };
 
 #define HIPCHK(expr)                                                                                             \
@@ -1211,6 +1213,110 @@ __global__ __launch_bounds__(BLOCK) void k_export_samples(DParams R, DSampler S,
     }
 }
 
+// ---- first-hit feature planes (pt_aov.h) ------------------------------------------------------------------------------------
+// Wave s works through segment s of round 0's extension queue behind k_extend_rf (mapped like k_generate: no ticket), in queue order
+// like epilogue_wave: path slots and hits of 64 consecutive positions are two coalesced reads; the values go to the path's slot.
+template <int FEAT>
+__global__ __launch_bounds__(BLOCK) void k_aov(DParams R, DCamera C, DScene sc, DPaths P, DQueues Q, DAov A, uint32_t off, uint32_t seg_cap, uint32_t G) { // off: the pass's first slot in A's arrays
+    const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (s >= G) return;
+    const uint32_t e0 = s * seg_cap;
+    const uint32_t n = rfl(*seg_count(Q, 0, Q_EXT, G, s));
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+        const uint32_t i = i0 + lane, e = e0 + i;
+        if (i >= n) continue;
+        const uint32_t pid = pslot(Q.ext[0], e);
+        const u4 r = pslot(P.hit, e);
+        const f2a pf = pslot(P.pfilm, pid);
+        const AovRec a = aov_item<FEAT>(R, C, sc, mk2(pf.x, pf.y), r);
+        const uint32_t q = off + pid;
+        pslot(A.albedo, q) = mkv4(a.albedo, a.coverage);
+        pslot(A.normal, q) = mkv4(a.normal, a.depth);
+        pslot(A.pos, q) = mkv4(a.p, u2f(a.prim));
+        if (A.depthp) pslot(A.depthp, q) = mkv4(mk3(a.depth, a.coverage, 0.0f), 0.0f);
+        if (A.pfilm) pslot(A.pfilm, q) = pf;
+    }
+}
+
+// The film gather of k_film for all planes of an AOV pass in one launch: one staging of the 20x20 apron, the footprint test and
+// film_weight_inside once per (sample, pixel), one accumulator per plane.  Per plane the additions are k_film's in k_film's order: a
+// plane's film equals, bit for bit, what k_film gives with P.L pointed at the plane's array.
+// Planes as accumulated: albedo.rgb | normal.rgb | (depth, coverage, 0); the weight of each is the filter-weight sum.
+__global__ __launch_bounds__(BLOCK) void k_film_aov(DParams R, DSampler S, DPaths P, DAov A, const float *__restrict__ table, DAovFilm F, int32_t y0, int32_t y1, int32_t tiles_x) {
+    __shared__ float tab[256];
+    __shared__ v4 s_p[400], s_al[400], s_n[400]; // p_film.xy - 0.5, depth, coverage | albedo.rgb | normal.rgb
+    __shared__ uint32_t s_m[400];                // footprint masks (k_film)
+    tab[threadIdx.x] = table[threadIdx.x];
+    const int32_t tx0 = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * 16, ty0 = y0 + (int32_t)(blockIdx.x / (uint32_t)tiles_x) * 16;
+    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
+    const int32_t x = tx0 + lx, y = ty0 + ly;
+    const bool live = x < R.W && y < y1;
+    const uint32_t my_bits = (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly));
+    const bool want_al = F.plane[AOV_ALBEDO] != nullptr, want_n = F.plane[AOV_NORMAL] != nullptr, want_d = F.plane[AOV_DEPTH] != nullptr;
+    const size_t px = (size_t)y * (size_t)R.W + (size_t)x;
+    v4 acc_al, acc_n, acc_d;
+    acc_al.x = acc_al.y = acc_al.z = acc_al.w = 0.0f; acc_n = acc_al; acc_d = acc_al;
+    if (live) {
+        if (want_al) acc_al = F.plane[AOV_ALBEDO][px];
+        if (want_n) acc_n = F.plane[AOV_NORMAL][px];
+        if (want_d) acc_d = F.plane[AOV_DEPTH][px];
+    }
+    const uint32_t npix = (uint32_t)(R.row1 - R.row0) * (uint32_t)R.NX;
+    const uint32_t ns = R.s1 - R.s0;
+    for (uint32_t k = 0; k < ns; ++k) {
+        __syncthreads(); // previous round's reads are done (and `tab` is visible on the first round)
+        for (uint32_t e = threadIdx.x; e < 400u; e += BLOCK) {
+            const int32_t sx = tx0 - 2 + (int32_t)(e % 20u) - S.min_x, sy = ty0 - 2 + (int32_t)(e / 20u) - S.min_y;
+            float pfx = -1.0e9f, pfy = -1.0e9f; // far away: no pixel is in its footprint
+            v4 al, nd; al.x = al.y = al.z = al.w = 0.0f; nd = al;
+            if (sx >= 0 && sx < R.NX && sy >= R.row0 && sy < R.row1) {
+                const uint32_t pid = k * npix + (uint32_t)(sy - R.row0) * (uint32_t)R.NX + (uint32_t)sx;
+                const f2a pf = pslot(P.pfilm, pid);
+                pfx = pf.x; pfy = pf.y; al = pslot(A.albedo, pid); nd = pslot(A.normal, pid);
+            }
+            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f; // film_weight's own first steps on the same values
+            const int32_t p0x = (int32_t)ceil_(pdx - 2.0f), p0y = (int32_t)ceil_(pdy - 2.0f), p1x = (int32_t)(floor_(pdx + 2.0f) + 1.0f), p1y = (int32_t)(floor_(pdy + 2.0f) + 1.0f);
+            auto span = [](int32_t lo, int32_t hi) { // bits [lo, hi) of a 16-bit field, both ends clipped to it
+                const uint32_t l = (uint32_t)(lo < 0 ? 0 : (lo > 16 ? 16 : lo)), h = (uint32_t)(hi < 0 ? 0 : (hi > 16 ? 16 : hi));
+                return h > l ? ((1u << h) - 1u) & ~((1u << l) - 1u) : 0u;
+            };
+            s_m[e] = span(p0x - tx0, p1x - tx0) | (span(p0y - ty0, p1y - ty0) << 16);
+            v4 a; a.x = pdx; a.y = pdy; a.z = nd.w; a.w = al.w; s_p[e] = a; s_al[e] = al; s_n[e] = nd;
+        }
+        __syncthreads();
+        if (live) {
+            for (int32_t dx = 0; dx < 5; ++dx)
+                for (int32_t dy = 0; dy < 5; ++dy) {
+                    const int32_t e = (ly + dy) * 20 + (lx + dx);
+                    if ((s_m[e] & my_bits) != my_bits) continue; // x < p0x || x >= p1x || y < p0y || y >= p1y
+                    const v4 a = s_p[e];
+                    const float w = film_weight_inside(a.x, a.y, x, y, tab);
+                    if (want_al) { const v4 c = s_al[e]; acc_al.x += c.x * w; acc_al.y += c.y * w; acc_al.z += c.z * w; acc_al.w += w; }
+                    if (want_n) { const v4 c = s_n[e]; acc_n.x += c.x * w; acc_n.y += c.y * w; acc_n.z += c.z * w; acc_n.w += w; }
+                    if (want_d) { acc_d.x += a.z * w; acc_d.y += a.w * w; acc_d.z += 0.0f * w; acc_d.w += w; }
+                }
+        }
+    }
+    if (live) {
+        if (want_al) F.plane[AOV_ALBEDO][px] = acc_al;
+        if (want_n) F.plane[AOV_NORMAL][px] = acc_n;
+        if (want_d) F.plane[AOV_DEPTH][px] = acc_d;
+    }
+}
+
+// ptrs_render_aov's per-sample export (k_export_samples' layout, 12 floats per sample)
+__global__ __launch_bounds__(BLOCK) void k_export_aov(DParams R, DSampler S, DAov A, uint32_t off, float *out) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t pid = blockIdx.x * BLOCK + threadIdx.x; pid < R.n_paths; pid += stride) {
+        const PathCoord c = path_coord(R, S, pid);
+        float *o = out + (((size_t)c.sy * (size_t)R.NX + (size_t)c.sx) * S.spp + c.s) * AOV_SAMPLE_FLOATS;
+        const v4 al = pslot(A.albedo, off + pid), nd = pslot(A.normal, off + pid), pp = pslot(A.pos, off + pid);
+        o[0] = al.x; o[1] = al.y; o[2] = al.z; o[3] = al.w;
+        o[4] = nd.x; o[5] = nd.y; o[6] = nd.z; o[7] = nd.w;
+        o[8] = pp.x; o[9] = pp.y; o[10] = pp.z; o[11] = pp.w;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -1388,12 +1494,18 @@ struct PtrsScene {
     DevBuf ws[MAX_LANES][32];   // per pipeline lane
     DevBuf counts[MAX_LANES], totals[MAX_LANES], tickets[MAX_LANES];
     DevBuf stats, table, film_tmp, samples_tmp, strat1, strat2, row_cost;
+    DevBuf aov_film_tmp[AOV_PLANES], aov_samples_tmp; // ptrs_render_aov: the host planes' device copies, the per-sample export
+    DevBuf aov_band[4], aov_band_pfilm;               // ptrs_render_aov in band mode (pt_aov.h): the values and p_film of one sample index of the whole band
     hipStream_t lane_stream[MAX_LANES] = {}; // lane 0 runs on the caller's stream, the others on these
     hipEvent_t lane_ev[MAX_LANES] = {};      // film-done per lane
     std::vector<hipEvent_t> ev_pool;
     int n_cu = 256;
     ~PtrsScene() {
         for (auto &b : {&stack_spill, &nodes2, &nodes4, &nodes, &tris, &shade, &mats, &texs, &levels, &texdata, &lights, &distdata, &inf, &stats, &table, &film_tmp, &samples_tmp, &strat1, &strat2, &row_cost}) b->release();
+        for (auto &b : aov_film_tmp) b.release();
+        for (auto &b : aov_band) b.release();
+        aov_band_pfilm.release();
+        aov_samples_tmp.release();
         for (auto &b : counts) b.release();
         for (auto &b : totals) b.release();
         for (auto &b : tickets) b.release();
@@ -1794,6 +1906,49 @@ struct HipBackend {
         *d.n_out = n < d.max_rays ? n : d.max_rays;
         cnt.release();
     }
+    // ---- first-hit feature planes (pt_aov.h): the values sit in path-state arrays of the shade / connect stages, which an AOV pass never runs
+    bool aov_band = false; // band mode: the values go to arrays of the whole band instead
+    int aov_band_begin(uint64_t n, std::string &err) {
+        for (auto &b : ps->aov_band) if ((rc = b.ensure((size_t)n * 16)) != PTRS_OK) { err = g_err + " (feature-plane band arrays)"; return rc; }
+        if ((rc = ps->aov_band_pfilm.ensure((size_t)n * 8)) != PTRS_OK) { err = g_err + " (feature-plane band arrays)"; return rc; }
+        aov_band = true;
+        return PTRS_OK;
+    }
+    DAov aov_arrays(bool depth_plane) const {
+        DAov A;
+        if (aov_band) { A.albedo = (v4 *)ps->aov_band[0].p; A.normal = (v4 *)ps->aov_band[1].p; A.pos = (v4 *)ps->aov_band[2].p; A.depthp = depth_plane ? (v4 *)ps->aov_band[3].p : nullptr; A.pfilm = (f2a *)ps->aov_band_pfilm.p; }
+        else { A.albedo = P.sh_o; A.normal = P.sh_d; A.pos = P.mis_o; A.depthp = depth_plane ? P.mis_d : nullptr; A.pfilm = nullptr; }
+        return A;
+    }
+    bool aov_depth_plane(uint32_t planes) const { return !opt.aov_fused_film && (planes & PTRS_AOV_DEPTH) != 0; } // the per-plane film launches read the depth plane as an array of its own
+    void aov(uint32_t planes, uint32_t off) {
+        t0(T_AUX);
+        const DAov A = aov_arrays(aov_depth_plane(planes));
+        if (feat == FEAT_SIMPLE) hipLaunchKernelGGL((k_aov<FEAT_SIMPLE>), dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, C, sc, P, Q, A, off, seg_cap, G);
+        else hipLaunchKernelGGL((k_aov<FEAT_FULL>), dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, C, sc, P, Q, A, off, seg_cap, G);
+        t1();
+    }
+    void film_aov(uint32_t planes, const DAovFilm &films, int32_t y0, int32_t y1, const DParams &Rf /* the sample rows and indices gathered: the pass, or in band mode one sample index of the band */) {
+        const int32_t tiles_x = (R.W + 15) / 16, tiles_y = (y1 - y0 + 15) / 16;
+        const DAov A = aov_arrays(aov_depth_plane(planes));
+        DPaths Pf = P;
+        if (A.pfilm) Pf.pfilm = A.pfilm;
+        if (n_lanes > 1 && film_prev) (void)hipStreamWaitEvent(stream, film_prev, 0); // pass order, whichever lane (film())
+        if (opt.aov_fused_film) {
+            DAovFilm F = films;
+            for (uint32_t k = 0; k < AOV_PLANES; ++k) if (!(planes & (1u << k))) F.plane[k] = nullptr;
+            t0(T_FILM); hipLaunchKernelGGL(k_film_aov, dim3((uint32_t)tiles_x * (uint32_t)tiles_y), dim3(BLOCK), 0, stream, Rf, S, Pf, A, (const float *)ps->table.p, F, y0, y1, tiles_x); t1();
+        } else {
+            v4 *const src[AOV_PLANES] = {A.albedo, A.normal, A.depthp};
+            for (uint32_t k = 0; k < AOV_PLANES; ++k) {
+                if (!(planes & (1u << k))) continue;
+                DPaths Pk = Pf; Pk.L = src[k]; // the unchanged film kernel with the plane as its radiance
+                t0(T_FILM); hipLaunchKernelGGL(k_film, dim3((uint32_t)tiles_x * (uint32_t)tiles_y), dim3(BLOCK), 0, stream, Rf, S, Pk, (const float *)ps->table.p, films.plane[k], y0, y1, tiles_x); t1();
+            }
+        }
+        if (n_lanes > 1) { film_prev = ps->lane_ev[cur]; (void)hipEventRecord(film_prev, stream); }
+    }
+    void export_aov(float *out, uint32_t off) { t0(T_FILM); hipLaunchKernelGGL(k_export_aov, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, aov_arrays(false), off, out); t1(); }
     void export_samples(float *out) { t0(T_FILM); hipLaunchKernelGGL(k_export_samples, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, P, out); t1(); }
     void end(PtrsStats &st) {
         for (uint32_t l = 0; l < n_lanes; ++l) { select(l); if (hipStreamSynchronize(stream) != hipSuccess) rc = PTRS_ERR_DEVICE; }
@@ -1839,6 +1994,30 @@ int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm,
     if (rc != PTRS_OK) return rc;
     std::string err;
     rc = render_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, film_dev, samples_dev, stats, err, progress, dump, single_pixel, row_cost_dev);
+    if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
+    if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
+    return PTRS_OK;
+}
+
+// ptrs_render_aov / ptrs_render_aov_device: the checks that need no device, then that there is one
+int aov_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, const void *const *plane_ptrs) {
+    if (!scene || !camera || !params) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
+    for (uint32_t k = 0; k < AOV_PLANES; ++k)
+        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
+    return PTRS_OK;
+}
+
+int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, uint32_t planes, const DAovFilm &films, float *samples_dev, hipStream_t stream, PtrsStats *stats) {
+    HIPCHK(hipSetDevice(ps->device));
+    HipBackend be;
+    be.ps = ps; be.stream = stream; be.opt = scene_options(ps); be.film_w = prm->width;
+    int rc = get_sobol(ps->device, &be.sob);
+    if (rc != PTRS_OK) return rc;
+    std::string err;
+    rc = render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err);
     if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
     if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
     return PTRS_OK;
@@ -1985,6 +2164,56 @@ static int render_samples_impl(PtrsScene *scene, const PtrsCamera *camera, const
     HIPCHK(hipMemcpy(film_inout + band_off, (PtrsFilmPixel *)scene->film_tmp.p + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
     if (sample_rgb) HIPCHK(hipMemcpy(sample_rgb, sdev, sbytes, hipMemcpyDeviceToHost));
     return PTRS_OK;
+}
+
+int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES],
+                           float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = aov_check_args(scene, camera, params, planes, (const void *const *)planes_inout_device);
+        if (rc != PTRS_OK) return rc;
+        DAovFilm F;
+        for (uint32_t k = 0; k < AOV_PLANES; ++k) F.plane[k] = (planes & (1u << k)) ? (v4 *)planes_inout_device[k] : nullptr;
+        return do_render_aov(scene, camera, params, planes, F, sample_aov_device, (hipStream_t)hip_stream, stats);
+    });
+}
+
+int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES],
+                    float *sample_aov, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = aov_check_args(scene, camera, params, planes, (const void *const *)planes_inout);
+        if (rc != PTRS_OK) return rc;
+        if (params->width <= 0 || params->height <= 0 || params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+        HIPCHK(hipSetDevice(scene->device));
+        // only the rows of the band travel, like ptrs_render_samples
+        int32_t rb = params->row_begin, re = params->row_end;
+        if (re <= rb) { rb = 0; re = params->height; }
+        if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
+        const size_t npx = (size_t)params->width * (size_t)params->height;
+        const size_t band_off = (size_t)rb * (size_t)params->width, band_px = (size_t)(re - rb) * (size_t)params->width;
+        DAovFilm F;
+        for (uint32_t k = 0; k < AOV_PLANES; ++k) {
+            F.plane[k] = nullptr;
+            if (!(planes & (1u << k))) continue;
+            if ((rc = scene->aov_film_tmp[k].ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
+            F.plane[k] = (v4 *)scene->aov_film_tmp[k].p;
+            HIPCHK(hipMemcpy((PtrsFilmPixel *)F.plane[k] + band_off, planes_inout[k] + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyHostToDevice));
+        }
+        float *sdev = nullptr; size_t sbytes = 0;
+        if (sample_aov) {
+            const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
+            const size_t spp = params->sampler == PTRS_SAMPLER_STRATIFIED ? (size_t)std::max(params->spp, 1) : (size_t)g.spp;
+            sbytes = (size_t)g.NX * (size_t)g.NY * spp * PTRS_AOV_SAMPLE_FLOATS * sizeof(float);
+            if ((rc = scene->aov_samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
+            HIPCHK(hipMemset(scene->aov_samples_tmp.p, 0, sbytes));
+            sdev = (float *)scene->aov_samples_tmp.p;
+        }
+        rc = do_render_aov(scene, camera, params, planes, F, sdev, nullptr, stats);
+        if (rc != PTRS_OK) return rc;
+        for (uint32_t k = 0; k < AOV_PLANES; ++k)
+            if (F.plane[k]) HIPCHK(hipMemcpy(planes_inout[k] + band_off, (PtrsFilmPixel *)F.plane[k] + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
+        if (sample_aov) HIPCHK(hipMemcpy(sample_aov, sdev, sbytes, hipMemcpyDeviceToHost));
+        return PTRS_OK;
+    });
 }
 
 int ptrs_render(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, PtrsStats *stats) {

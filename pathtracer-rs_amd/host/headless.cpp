@@ -25,7 +25,7 @@ static bool parse_resolution(const char *s, int &w, int &h) { // main.rs:23-33
 
 int main(int argc, char **argv) {
     std::string scene_path, out_dir, dump_path, dump_full_path, env_map_path;
-    bool default_lights = false, even_bands = false, preview = false, progress = false;
+    bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false;
     int n_gpus = 1;
     int spp = 1, max_depth = 15, w = 640, h = 480; // DEFAULT_RESOLUTION common/mod.rs:14
     bool have_out = false;
@@ -45,13 +45,14 @@ int main(int argc, char **argv) {
         else if (a == "--preview") preview = true;                     // DIR/render.png is rewritten after every pass (the reference pushes the partial film to tev, headless.rs:197-214)
         else if (a == "--progress") progress = true;                   // a progress line per pass (the reference's progress bar, integrator.rs:631-634); like --preview it
                                                                        // renders through ptrs_render_progressive, which publishes the film after every pass (slower than the one-shot render)
+        else if (a == "--aov") aov = true;                             // next to render.png: albedo.png, normal.png, depth.png (the first-hit planes of ptrs_render_aov, resolved)
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
         else scene_path = a;
     }
     if (scene_path.empty() || (!have_out && dump_path.empty() && dump_full_path.empty())) {
-        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--headless]\n");
+        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--headless]\n");
         return 2;
     }
     Camera camera; RenderScene scene; std::string err;
@@ -85,5 +86,17 @@ int main(int argc, char **argv) {
     const std::string out = out_dir + "/render.png"; // main.rs:70
     if (!write_png_rgba8(out, camera.film.width, camera.film.height, camera.film.to_rgba_image(), err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     std::fprintf(stderr, "INFO wrote %s\n", out.c_str());
+    if (aov) {
+        std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES];
+        rc = integrator.render_aov(camera, scene, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, &st);
+        if (rc != PTRS_OK) { std::fprintf(stderr, "error: aov render failed (%d): %s\n", rc, integrator.last_error.c_str()); return 1; }
+        std::vector<uint8_t> img[PTRS_AOV_PLANES];
+        aov_to_rgba_images(camera.film.width, camera.film.height, planes, img);
+        const char *names[PTRS_AOV_PLANES] = {"/albedo.png", "/normal.png", "/depth.png"};
+        for (int k = 0; k < PTRS_AOV_PLANES; ++k) {
+            if (!write_png_rgba8(out_dir + names[k], camera.film.width, camera.film.height, img[k], err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+            std::fprintf(stderr, "INFO wrote %s%s\n", out_dir.c_str(), names[k]);
+        }
+    }
     return 0;
 }

@@ -95,15 +95,74 @@ PtrsRenderParams PathIntegrator::params(const Camera &camera) const {
     p.row_begin = 0; p.row_end = camera.film.height; p.device = device_; p.paths_per_pass = 0; p.flags = 0;
     return p;
 }
-int PathIntegrator::render(Camera &camera, RenderScene &scene, PtrsStats *stats) {
+int PathIntegrator::ensure_scene(RenderScene &scene) {
     if (!gpu_scene_ || gpu_scene_src_ != &scene) {
         if (gpu_scene_) { ptrs_scene_destroy(gpu_scene_); gpu_scene_ = nullptr; }
         int rc = ptrs_scene_create(&scene.desc(), device_, &gpu_scene_);
         if (rc != PTRS_OK) { last_error = ptrs_last_error(); return rc; }
         gpu_scene_src_ = &scene;
     }
+    return PTRS_OK;
+}
+int PathIntegrator::render_aov(Camera &camera, RenderScene &scene, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
     const PtrsRenderParams p = params(camera);
-    int rc;
+    const size_t npx = (size_t)camera.film.width * (size_t)camera.film.height;
+    PtrsFilmPixel *ptrs[PTRS_AOV_PLANES] = {nullptr, nullptr, nullptr};
+    for (uint32_t k = 0; k < PTRS_AOV_PLANES; ++k) {
+        if (!(planes & (1u << k))) continue;
+        if (planes_inout[k].size() != npx) planes_inout[k].assign(npx, PtrsFilmPixel{{0, 0, 0}, 0});
+        ptrs[k] = planes_inout[k].data();
+    }
+    rc = ptrs_render_aov(gpu_scene_, &camera.abi, &p, planes, ptrs, nullptr, stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
+void aov_to_rgba_images(int w, int h, const std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<uint8_t> rgba_out[PTRS_AOV_PLANES]) {
+    const size_t npx = (size_t)w * (size_t)h;
+    const std::vector<PtrsFilmPixel> &al = planes[0], &nr = planes[1], &dp = planes[2];
+    auto code = [](double v) { v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); return (uint8_t)std::floor(255.0 * v + 0.5); };
+    std::vector<uint8_t> alpha(npx, 255);
+    std::vector<double> depth(npx, 0.0);
+    double max_depth = 0.0;
+    if (dp.size() == npx)
+        for (size_t i = 0; i < npx; ++i) {
+            alpha[i] = dp[i].weight != 0.0f ? code((double)dp[i].rgb[1] / (double)dp[i].weight) : 0;
+            depth[i] = dp[i].rgb[1] != 0.0f ? (double)dp[i].rgb[0] / (double)dp[i].rgb[1] : 0.0;
+            if (depth[i] > max_depth) max_depth = depth[i];
+        }
+    for (int k = 0; k < PTRS_AOV_PLANES; ++k) rgba_out[k].clear();
+    if (al.size() == npx) {
+        rgba_out[0].resize(npx * 4);
+        for (size_t i = 0; i < npx; ++i) {
+            for (int c = 0; c < 3; ++c) rgba_out[0][i * 4 + c] = al[i].weight != 0.0f ? code((double)al[i].rgb[c] / (double)al[i].weight) : 0;
+            rgba_out[0][i * 4 + 3] = alpha[i];
+        }
+    }
+    if (nr.size() == npx) {
+        rgba_out[1].resize(npx * 4);
+        for (size_t i = 0; i < npx; ++i) {
+            double n[3] = {0.0, 0.0, 0.0};
+            if (nr[i].weight != 0.0f) for (int c = 0; c < 3; ++c) n[c] = (double)nr[i].rgb[c] / (double)nr[i].weight;
+            const double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            for (int c = 0; c < 3; ++c) rgba_out[1][i * 4 + c] = code(0.5 * (l > 0.0 ? n[c] / l : 0.0) + 0.5);
+            rgba_out[1][i * 4 + 3] = alpha[i];
+        }
+    }
+    if (dp.size() == npx) {
+        rgba_out[2].resize(npx * 4);
+        for (size_t i = 0; i < npx; ++i) {
+            const uint8_t v = max_depth > 0.0 ? code(depth[i] / max_depth) : 0;
+            rgba_out[2][i * 4] = rgba_out[2][i * 4 + 1] = rgba_out[2][i * 4 + 2] = v;
+            rgba_out[2][i * 4 + 3] = alpha[i];
+        }
+    }
+}
+int PathIntegrator::render(Camera &camera, RenderScene &scene, PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    const PtrsRenderParams p = params(camera);
     if (on_pass || show_progress_bar_) { // integrator.rs:631-634 (progress bar) / headless.rs:197-214 (film read while rendering): the film is published pass by pass
         struct Ctx { PathIntegrator *self; } ctx{this};
         auto thunk = [](void *user, uint32_t done, uint32_t total, int32_t y0, int32_t y1) {

@@ -92,6 +92,9 @@ public:
     void toggle_progress_bar() { show_progress_bar_ = !show_progress_bar_; }
     // integrator.rs:536-642 on the GPU; accumulates into camera.film.  Returns PTRS_OK or an error code.
     int render(Camera &camera, RenderScene &scene, PtrsStats *stats = nullptr);
+    // ptrs_render_aov: the first-hit feature planes of the same view (plane k = bit k of `planes`: PTRS_AOV_ALBEDO | _NORMAL | _DEPTH),
+    // accumulated into planes_inout[k] (resized to the film and cleared when its size does not fit).  max_depth plays no part.
+    int render_aov(Camera &camera, RenderScene &scene, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats = nullptr);
     // When set, render() publishes the film after every pass of the pipeline (ptrs_render_progressive) and calls this with
     // (passes done, passes in total, first row, one past the last row that changed): the hook a preview gets instead of the
     // reference's second thread that reads the film every 2 s (headless.rs:197-214).
@@ -118,7 +121,14 @@ private:
     std::string plan_key_;          // the view (camera, resolution, depth, device count) plan_ was made for
     std::vector<int32_t> plan_;     // its row bounds
     PtrsRenderParams params(const Camera &camera) const;
+    int ensure_scene(RenderScene &scene);
 };
+
+// The planes of render_aov resolved for display, RGBA8 each (alpha = covered weight / weight in all three):
+//   albedo round(255 clamp(rgb / weight, 0, 1)), normal round(255 (0.5 n + 0.5)) with n = rgb / weight renormalised where non-zero,
+//   depth  round(255 depth / max depth) in r, g, b with depth = r / g (mean depth over the covered weight; 0 where g == 0).
+// depth_plane supplies the alpha of all three; an empty plane gives an empty image.
+void aov_to_rgba_images(int w, int h, const std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<uint8_t> rgba_out[PTRS_AOV_PLANES]);
 
 // Per-row cost of a frame for band planning: the BVH queries of every sample row's paths in ONE 1-spp render with device counters
 // (ptrs_render_row_cost: a few milliseconds).  Returns false and fills err on failure.

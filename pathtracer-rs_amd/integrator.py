@@ -216,6 +216,50 @@ class PathIntegrator:
         self.last_stats = stats
         return stats
 
+    def render_aov(self, camera, scene, planes=("albedo", "normal", "depth"), row_begin=0, row_end=0, want_samples=False, into=None):
+        """ptrs_render_aov: the first-hit feature planes of this integrator's view, filtered onto the film by the samples and weights
+        of render() (max_depth plays no part).  Returns a dict name -> (H, W) FILM_DTYPE array of accumulated sums (resolve_aov turns
+        them into displayable values); planes given in `into` are accumulated into, the others start from zero.  With want_samples
+        returns (planes, samples), samples of shape (H + 4, W + 4, spp, 12): albedo, coverage, normal, depth, position, triangle id bits."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, out = _aov_mask(planes), {}
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)()
+        for k, name in enumerate(abi.PtrsAovNames):
+            if mask & (1 << k):
+                a = into.get(name) if into else None
+                if a is None:
+                    a = np.zeros((p.height, p.width), dtype=abi.FILM_DTYPE)
+                if a.dtype != abi.FILM_DTYPE or a.shape != (p.height, p.width) or not a.flags.c_contiguous:
+                    raise PtrsError("render_aov: plane %s must be a contiguous (H, W) FILM_DTYPE array" % name)
+                out[name] = a
+                ptrs[k] = a.ctypes.data
+        samples = None
+        if want_samples:
+            samples = np.zeros((p.height + 4, p.width + 4, p.spp if p.sampler == abi.SAMPLER_STRATIFIED else round_up_pow2(p.spp), abi.PtrsAovSampleFloats), dtype=np.float32)
+        _check(load_library().ptrs_render_aov(ds.handle, C.byref(cam), C.byref(p), C.c_uint32(mask), ptrs,
+                                              C.c_void_p(samples.ctypes.data) if want_samples else None, C.byref(stats)))
+        self.last_stats = stats
+        return (out, samples) if want_samples else out
+
+    def render_aov_device(self, camera, scene, plane_device_ptrs, planes=("albedo", "normal", "depth"), stream=0, row_begin=0, row_end=0, flags=0, samples_device_ptr=0):
+        """Same, the planes' accumulators in device memory: plane_device_ptrs maps a plane's name to the address of width*height*16 bytes."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end, flags)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask = _aov_mask(planes)
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)()
+        for k, name in enumerate(abi.PtrsAovNames):
+            if mask & (1 << k) and plane_device_ptrs.get(name):
+                ptrs[k] = int(plane_device_ptrs[name])
+        _check(load_library().ptrs_render_aov_device(ds.handle, C.byref(cam), C.byref(p), C.c_uint32(mask), ptrs,
+                                                     C.c_void_p(int(samples_device_ptr)) if samples_device_ptr else None, C.c_void_p(int(stream)), C.byref(stats)))
+        self.last_stats = stats
+        return stats
+
     def render_progressive(self, camera, scene, on_pass, row_begin=0, row_end=0):
         """ptrs_render_progressive: like render(), and after every pass of the pipeline the rows it touched are copied into
         camera.film.pixels and on_pass(passes_done, passes_total, row_begin, row_end) is called (the preview hook the
@@ -269,6 +313,38 @@ class PathIntegrator:
         self.last_single_pixel_paths = round_up_pow2(p.spp)
         _check(load_library().ptrs_render_single_pixel(ds.handle, C.byref(cam), C.byref(p), int(pixel[0]), int(pixel[1]), C.c_void_p(out.ctypes.data)))
         return out
+
+
+def _aov_mask(planes):
+    mask = 0
+    for name in planes:
+        if name not in abi.PtrsAovNames:
+            raise PtrsError("unknown AOV plane %r (albedo, normal, depth)" % (name,))
+        mask |= 1 << abi.PtrsAovNames.index(name)
+    return mask
+
+
+def resolve_aov(planes):
+    """The accumulated planes of render_aov as displayable float64 arrays: albedo = rgb / weight; normal = rgb / weight, renormalised
+    where non-zero; depth = r / g of the depth plane (mean depth over the covered weight, 0 where nothing is covered); alpha = g / weight
+    of the depth plane.  Pixels without weight give 0."""
+    def ratio(num, den):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.zeros_like(num), where=den != 0)
+    out = {}
+    if "albedo" in planes:
+        a = planes["albedo"]
+        out["albedo"] = ratio(a["rgb"], a["weight"][..., None] * np.ones(3))
+    if "normal" in planes:
+        a = planes["normal"]
+        n = ratio(a["rgb"], a["weight"][..., None] * np.ones(3))
+        l = np.sqrt((n * n).sum(axis=-1, keepdims=True))
+        out["normal"] = ratio(n, l * np.ones(3))
+    if "depth" in planes:
+        a = planes["depth"]
+        out["depth"] = ratio(a["rgb"][..., 0], a["rgb"][..., 1])
+        out["alpha"] = ratio(a["rgb"][..., 1], a["weight"])
+    return out
 
 
 def trace_rays(scene, rays, any_hit=False, device=0, bvh=None):
