@@ -210,7 +210,7 @@ typedef struct PtrsStats {
     /* PTRS_FLAG_COUNTERS, lane-refill traversal kernels: lane occupancy of the two phases =
      * node_visits / node_steps_x64 and tris_tested (of these kernels) / tri_steps_x64 */
     uint64_t node_steps_x64, node_visits, tri_steps_x64;
-    uint64_t debug[12];      /* zero in product builds; diagnostic builds (-DPTRS_STAMPS): wave-clock sums per phase of k_shade */
+    uint64_t debug[12];      /* zero in product builds; diagnostic builds (-DPTRS_STAMPS): wave-clock sums per phase of k_shade; ptrs_denoise with PTRS_DENOISE_TIMING: nanoseconds per launch */
     /* how the queue kernels of the call's last pass were launched (ABI 3): segments per queue (one wave each), and per kernel class
      * [0] extend, [1] connect, [2] shade, [3] aux the workgroups of the last launch and the resident workgroups per CU the launch was
      * sized for (hipOccupancyMaxActiveBlocksPerMultiprocessor) */
@@ -331,6 +331,36 @@ int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRender
                     PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats);
 int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes,
                            void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats);
+
+/* Edge-avoiding a-trous denoiser of a low-spp film, guided by the three planes of ptrs_render_aov (no counterpart in the reference;
+ * the contract is DESIGN.md section 11).  Inputs: four accumulated films of width x height pixels -- beauty (ptrs_render) and the
+ * albedo, normal and depth planes, all three required; they are never written.  out (width x height, not one of the inputs) receives
+ * rgb = the filtered colour, weight = 1; a pixel without weight gives zeros.  iterations: 1 .. PTRS_DENOISE_MAX_ITERATIONS, iteration i
+ * has taps 2^i pixels apart and colour sigma sigma_color / 2^i; a sigma <= 0 drops its term.  PTRS_DENOISE_DEMODULATE: the colour is
+ * divided by the albedo before the filter and multiplied by it afterwards.  A PtrsDenoiser owns the workspace (64 bytes per pixel) of
+ * one device for one width x height; one call at a time per denoiser.  It never touches a PtrsScene.  The argument checks are made
+ * before the first device call.  stats (may be NULL): ms_total, kernel_launches and device_bytes, everything else 0 (PTRS_DENOISE_TIMING apart).  The _device form
+ * takes the films in device memory and a stream, and returns after the stream has drained.  Option "denoise_lds" (-1 = by step, 0, 1)
+ * selects between two forms of the iteration kernel (direct loads / an LDS-staged tile, steps up to 16); it changes no bit. */
+#define PTRS_DENOISE_MAX_ITERATIONS 8
+enum {
+    PTRS_DENOISE_DEMODULATE = 1u,
+    PTRS_DENOISE_TIMING = 2u /* measurement hook (tools/denoise_cost.py): hipEvent time of every launch of the call, in nanoseconds, in
+                                stats->debug: [0] prepare, [1 + i] iteration i, [9] finish.  Changes no bit of the output */
+};
+typedef struct PtrsDenoiseParams {
+    int32_t iterations;
+    float sigma_color, sigma_normal, sigma_depth;
+    uint32_t flags; /* PTRS_DENOISE_* */
+} PtrsDenoiseParams;
+typedef struct PtrsDenoiser PtrsDenoiser;
+void ptrs_denoise_default_params(PtrsDenoiseParams *p); /* 5 iterations, sigmas 0.25 / 0.3 / 0.1, demodulation on */
+int ptrs_denoiser_create(int32_t device, int32_t width, int32_t height, PtrsDenoiser **out);
+void ptrs_denoiser_destroy(PtrsDenoiser *d);
+int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixel *beauty,
+                 const PtrsFilmPixel *const planes[PTRS_AOV_PLANES], PtrsFilmPixel *out, PtrsStats *stats); /* host memory */
+int ptrs_denoise_device(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty_device,
+                        const void *const planes_device[PTRS_AOV_PLANES], void *out_device, void *hip_stream, PtrsStats *stats);
 
 /* PathIntegrator::render_single_pixel (integrator.rs:505-534): radiance of every sample of one
  * pixel, rgb_out[spp*3]. */

@@ -96,6 +96,12 @@ class PtrsHit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("t", C.c_float), ("b0", C.c_float), ("b1", C.c_float), ("b2", C.c_float)]
 
 
+class PtrsDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
+PtrsDenoiseDemodulate, PtrsDenoiseTiming, PtrsDenoiseMaxIterations = 1, 2, 8
+
 HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4")])
 FILM_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4")])
 

@@ -23,6 +23,7 @@
 
 #include "pt_render.h"
 #include "pt_aov.h"
+#include "pt_denoise.h"
 #include "pt_probe.h"
 
 using namespace pt;
@@ -63,6 +64,7 @@ struct Options {
     int tail_paths = 0;       // (tail_at = -1) paths per segment at or below which the tail takes over; 0 = the measured default (TAIL_PATHS_DEFAULT)
     int workspace_pct = 40;   // the render workspace (path state + queues of all lanes) may take this share of the device memory that is free at the call
     int aov_fused_film = 1;   // ptrs_render_aov: the planes' films are gathered by ONE k_film_aov launch per pass; 0: one k_film launch per plane (same bits)
+    int denoise_lds = -1;     // ptrs_denoise: iteration kernel form for steps up to DN_LDS_MAX_STEP: 0 direct global loads, 1 the LDS-staged tile, -1 = by step (DN_LDS_DEFAULT_STEPS); same bits
 };
 Options g_opt;
 std::mutex g_opt_mu;
@@ -70,7 +72,7 @@ Options options() { std::lock_guard<std::mutex> lk(g_opt_mu); return g_opt; }
 struct OptionDesc { const char *name; int Options::*field; int lo, hi; };
 const OptionDesc k_options[] = {
     {"lanes", &Options::lanes, 0, 8}, {"refill", &Options::refill, -1, 64}, {"refill_connect", &Options::refill_connect, -1, 64}, {"stack_lds", &Options::stack_lds, 8, 16},
-    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20}, {"aov_fused_film", &Options::aov_fused_film, 0, 1},
+    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20}, {"aov_fused_film", &Options::aov_fused_film, 0, 1}, {"denoise_lds", &Options::denoise_lds, -1, 1},
 };
 
 #define HIPCHK(expr)                                                                                             \
@@ -1317,6 +1319,69 @@ __global__ __launch_bounds__(BLOCK) void k_export_aov(DParams R, DSampler S, DAo
     }
 }
 
+// ---- denoiser (pt_denoise.h): prepare, `iterations` a-trous launches over ping / pong, finish ------------------------------------
+// No queues, no atomics, nothing to spin on: one thread per pixel, every tap bounds-checked.  The iteration kernel has two forms over
+// the same per-pixel function (dn_atrous), which differ in where a tap comes from:
+//   k_dn_iter        a workgroup is 64 x 4 pixels, lanes are neighbours in x, every tap is two 16-byte global loads
+//   k_dn_iter_lds<S> for step S the rows y = r (mod S) form an image of their own with unit row step: a workgroup stages 64 + 4 S
+//                    contiguous columns x DN_TILE_T + 4 lattice rows of colour and guide in LDS and filters 64 x DN_TILE_T outputs
+//                    out of it; pixels beyond the image are staged as empty ones.  (64 + 4 S)(T + 4) 32 B: 17 KiB at S = 1, 48 KiB at
+//                    S = 16, the largest step instantiated -- beyond it the tile would not leave room for several workgroups on a CU.
+enum : int { DN_TILE_W = 64, DN_TILE_T = 8, DN_LDS_MAX_STEP = 16 };
+enum : uint32_t { DN_LDS_DEFAULT_STEPS = 0u }; // option denoise_lds = -1: the steps (a bit mask) whose shipped form is the LDS tile (the measurement)
+
+__global__ __launch_bounds__(BLOCK) void k_dn_prepare(uint32_t n, const v4 *__restrict__ B, const v4 *__restrict__ A, const v4 *__restrict__ N, const v4 *__restrict__ D,
+                                                      v4 *__restrict__ x, v4 *__restrict__ g, v4 *__restrict__ a, int demodulate) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const DnPixel o = dn_prepare(B[i], A[i], N[i], D[i], demodulate != 0);
+    x[i] = o.x; g[i] = o.g; a[i] = o.a;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_dn_iter(DnIter it, const v4 *__restrict__ xin, const v4 *__restrict__ gin, v4 *__restrict__ xout) {
+    const int32_t px = (int32_t)blockIdx.x * 64 + (int32_t)(threadIdx.x & 63u), py = (int32_t)blockIdx.y * WAVES + (int32_t)(threadIdx.x >> 6);
+    if (px >= it.W || py >= it.H) return;
+    const uint32_t p = (uint32_t)py * (uint32_t)it.W + (uint32_t)px;
+    auto fetch = [&](int dx, int dy, v4 &xq, v4 &gq) -> bool {
+        const int32_t qx = px + it.step * dx, qy = py + it.step * dy;
+        if (qx < 0 || qx >= it.W || qy < 0 || qy >= it.H) return false;
+        const uint32_t q = (uint32_t)qy * (uint32_t)it.W + (uint32_t)qx;
+        xq = xin[q]; gq = gin[q];
+        return dn_ok(xq);
+    };
+    xout[p] = dn_atrous(it, xin[p], gin[p], fetch);
+}
+
+template <int S>
+__global__ __launch_bounds__(BLOCK) void k_dn_iter_lds(DnIter it, const v4 *__restrict__ xin, const v4 *__restrict__ gin, v4 *__restrict__ xout) {
+    constexpr int COLS = DN_TILE_W + 4 * S, ROWS = DN_TILE_T + 4;
+    __shared__ v4 sx[ROWS * COLS], sg[ROWS * COLS];
+    const int32_t r = (int32_t)blockIdx.z, x0 = (int32_t)blockIdx.x * DN_TILE_W, j0 = (int32_t)blockIdx.y * DN_TILE_T; // residue, first column, first lattice row
+    if (r + S * j0 >= it.H) return; // (the whole workgroup: no output row)
+    for (int idx = (int)threadIdx.x; idx < ROWS * COLS; idx += BLOCK) {
+        const int row = idx / COLS, col = idx - row * COLS;
+        const int32_t gx = x0 - 2 * S + col, gy = r + S * (j0 - 2 + row);
+        v4 xv = mkv4(splat3(0.0f), dn_empty_mark()), gv = mkv4(splat3(0.0f), 0.0f);
+        if (gx >= 0 && gx < it.W && gy >= 0 && gy < it.H) { const uint32_t q = (uint32_t)gy * (uint32_t)it.W + (uint32_t)gx; xv = xin[q]; gv = gin[q]; }
+        sx[idx] = xv; sg[idx] = gv;
+    }
+    __syncthreads();
+    const int lx = (int)(threadIdx.x & 63u);
+    const int32_t px = x0 + lx;
+    for (int k = (int)(threadIdx.x >> 6); k < DN_TILE_T; k += WAVES) {
+        const int32_t py = r + S * (j0 + k);
+        if (px >= it.W || py >= it.H) continue;
+        const int c = (k + 2) * COLS + lx + 2 * S;
+        auto fetch = [&](int dx, int dy, v4 &xq, v4 &gq) -> bool { const int q = c + dy * COLS + dx * S; xq = sx[q]; gq = sg[q]; return dn_ok(xq); };
+        xout[(uint32_t)py * (uint32_t)it.W + (uint32_t)px] = dn_atrous(it, sx[c], sg[c], fetch);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_dn_finish(uint32_t n, const v4 *__restrict__ x, const v4 *__restrict__ a, v4 *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) out[i] = dn_finish(x[i], a[i]);
+}
+
 __global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -1514,6 +1579,16 @@ struct PtrsScene {
         for (auto e : lane_ev) if (e) (void)hipEventDestroy(e);
         for (auto e : ev_pool) (void)hipEventDestroy(e);
     }
+};
+
+// ptrs_denoiser_create makes no device call (its argument checks, and those of ptrs_denoise, work without a device); the buffers
+// grow at the first call that needs them.
+struct PtrsDenoiser {
+    int device = 0;
+    int32_t W = 0, H = 0;
+    DevBuf ws;       // 64 bytes per pixel: colour ping, colour pong, guide, albedo
+    DevBuf stage[5]; // ptrs_denoise: the host films' device copies (beauty, the three planes, out)
+    ~PtrsDenoiser() { ws.release(); for (auto &b : stage) b.release(); }
 };
 
 namespace {
@@ -2023,6 +2098,78 @@ int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *
     return PTRS_OK;
 }
 
+// ptrs_denoise / ptrs_denoise_device: the checks that need no device
+int dn_check_args(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty, const void *const *planes, const void *out) {
+    if (!d || !p || !beauty || !planes || !out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    for (uint32_t k = 0; k < AOV_PLANES; ++k) if (!planes[k]) { g_err = "null plane pointer (the denoiser needs all three planes)"; return PTRS_ERR_INVALID; }
+    if (const char *m = dn_check_params(*p)) { g_err = m; return PTRS_ERR_INVALID; }
+    if (out == beauty || out == planes[0] || out == planes[1] || out == planes[2]) { g_err = "out must not be one of the inputs"; return PTRS_ERR_INVALID; }
+    return PTRS_OK;
+}
+int dn_select_device(PtrsDenoiser *d) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
+    if (d->device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
+    HIPCHK(hipSetDevice(d->device));
+    return PTRS_OK;
+}
+
+template <int S> void dn_launch_lds(const DnIter &it, const v4 *xin, const v4 *gin, v4 *xout, hipStream_t stream) {
+    const uint32_t lattice_rows = ((uint32_t)it.H + (uint32_t)S - 1u) / (uint32_t)S; // of residue 0, the longest
+    hipLaunchKernelGGL((k_dn_iter_lds<S>), dim3(((uint32_t)it.W + DN_TILE_W - 1u) / DN_TILE_W, (lattice_rows + DN_TILE_T - 1u) / DN_TILE_T, (uint32_t)S), dim3(BLOCK), 0, stream, it, xin, gin, xout);
+}
+
+// device films in, device film out, on `stream`; returns with the stream drained
+int do_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const v4 *B, const v4 *const planes[AOV_PLANES], v4 *out, hipStream_t stream, PtrsStats *stats, size_t staged_bytes) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    const size_t npx = (size_t)d->W * (size_t)d->H;
+    if (npx >= (1ull << 31)) { g_err = "film too large for the denoiser"; return PTRS_ERR_UNSUPPORTED; }
+    int rc = d->ws.ensure(npx * 64);
+    if (rc != PTRS_OK) return rc;
+    v4 *x[2] = {(v4 *)d->ws.p, (v4 *)d->ws.p + npx}, *g = (v4 *)d->ws.p + 2 * npx, *a = (v4 *)d->ws.p + 3 * npx;
+    const Options opt = options();
+    const uint32_t n = (uint32_t)npx, grid = (n + BLOCK - 1u) / BLOCK;
+    uint64_t launches = 0;
+    std::vector<hipEvent_t> ev; // PTRS_DENOISE_TIMING: one event before the first launch and one behind every launch
+    auto stamp = [&]() { if (p->flags & PTRS_DENOISE_TIMING) { hipEvent_t e = nullptr; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, stream); ev.push_back(e); } } };
+    stamp();
+    hipLaunchKernelGGL(k_dn_prepare, dim3(grid), dim3(BLOCK), 0, stream, n, B, planes[AOV_ALBEDO], planes[AOV_NORMAL], planes[AOV_DEPTH], x[0], g, a, (p->flags & PTRS_DENOISE_DEMODULATE) ? 1 : 0);
+    ++launches; stamp();
+    int cur = 0;
+    for (int i = 0; i < p->iterations; ++i, cur ^= 1) {
+        const DnIter it = dn_iter(*p, d->W, d->H, i);
+        const bool lds = it.step <= DN_LDS_MAX_STEP && (opt.denoise_lds == 1 || (opt.denoise_lds < 0 && (DN_LDS_DEFAULT_STEPS & (uint32_t)it.step) != 0u));
+        if (!lds) hipLaunchKernelGGL(k_dn_iter, dim3(((uint32_t)d->W + 63u) / 64u, ((uint32_t)d->H + WAVES - 1u) / WAVES), dim3(BLOCK), 0, stream, it, (const v4 *)x[cur], (const v4 *)g, x[cur ^ 1]);
+        else switch (it.step) {
+            case 1: dn_launch_lds<1>(it, x[cur], g, x[cur ^ 1], stream); break;
+            case 2: dn_launch_lds<2>(it, x[cur], g, x[cur ^ 1], stream); break;
+            case 4: dn_launch_lds<4>(it, x[cur], g, x[cur ^ 1], stream); break;
+            case 8: dn_launch_lds<8>(it, x[cur], g, x[cur ^ 1], stream); break;
+            default: dn_launch_lds<16>(it, x[cur], g, x[cur ^ 1], stream); break;
+        }
+        ++launches; stamp();
+    }
+    hipLaunchKernelGGL(k_dn_finish, dim3(grid), dim3(BLOCK), 0, stream, n, (const v4 *)x[cur], (const v4 *)a, out);
+    ++launches; stamp();
+    const hipError_t e_launch = hipGetLastError(), e_sync = hipStreamSynchronize(stream);
+    uint64_t ns[12] = {0};
+    for (size_t k = 0; k + 1 < ev.size() && ev.size() == launches + 1; ++k) { // [0] prepare, [1 + i] iteration i, [9] finish
+        float ms = 0.0f;
+        if (e_sync == hipSuccess && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) ns[k + 1 == launches ? 9 : k] = (uint64_t)((double)ms * 1e6);
+    }
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    HIPCHK(e_launch);
+    HIPCHK(e_sync);
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        std::memcpy(stats->debug, ns, sizeof(ns));
+        stats->kernel_launches = launches;
+        stats->device_bytes = npx * 64 + staged_bytes;
+        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return PTRS_OK;
+}
+
 // extern "C" entry points never let an exception (std::bad_alloc from a host vector, ...) cross the boundary
 template <class F> int guarded(F &&f) {
     try { return f(); }
@@ -2048,7 +2195,7 @@ int ptrs_abi_sizeof(int which) {
         case 0: return (int)sizeof(PtrsTexture); case 1: return (int)sizeof(PtrsMaterial); case 2: return (int)sizeof(PtrsMesh);
         case 3: return (int)sizeof(PtrsLight); case 4: return (int)sizeof(PtrsBvhNode); case 5: return (int)sizeof(PtrsSceneDesc);
         case 6: return (int)sizeof(PtrsCamera); case 7: return (int)sizeof(PtrsRenderParams); case 8: return (int)sizeof(PtrsStats);
-        case 9: return (int)sizeof(PtrsHit); case 10: return (int)sizeof(PtrsFilmPixel);
+        case 9: return (int)sizeof(PtrsHit); case 10: return (int)sizeof(PtrsFilmPixel); case 11: return (int)sizeof(PtrsDenoiseParams);
         default: return -1;
     }
 }
@@ -2212,6 +2359,55 @@ int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRender
         for (uint32_t k = 0; k < AOV_PLANES; ++k)
             if (F.plane[k]) HIPCHK(hipMemcpy(planes_inout[k] + band_off, (PtrsFilmPixel *)F.plane[k] + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
         if (sample_aov) HIPCHK(hipMemcpy(sample_aov, sdev, sbytes, hipMemcpyDeviceToHost));
+        return PTRS_OK;
+    });
+}
+
+void ptrs_denoise_default_params(PtrsDenoiseParams *p) {
+    if (!p) return;
+    p->iterations = 5; p->sigma_color = 0.25f; p->sigma_normal = 0.3f; p->sigma_depth = 0.1f; p->flags = PTRS_DENOISE_DEMODULATE;
+}
+
+int ptrs_denoiser_create(int32_t device, int32_t width, int32_t height, PtrsDenoiser **out) {
+    return guarded([&]() -> int {
+        if (!out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (width <= 0 || height <= 0) { g_err = "denoiser width and height must be positive"; return PTRS_ERR_INVALID; }
+        if (device < 0) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
+        PtrsDenoiser *d = new PtrsDenoiser();
+        d->device = device; d->W = width; d->H = height;
+        *out = d;
+        return PTRS_OK;
+    });
+}
+
+void ptrs_denoiser_destroy(PtrsDenoiser *d) {
+    if (!d) return;
+    if (d->ws.p || d->stage[0].p) (void)hipSetDevice(d->device);
+    delete d;
+}
+
+int ptrs_denoise_device(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty_device, const void *const planes_device[PTRS_AOV_PLANES], void *out_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = dn_check_args(d, p, beauty_device, planes_device, out_device);
+        if (rc != PTRS_OK || (rc = dn_select_device(d)) != PTRS_OK) return rc;
+        const v4 *planes[AOV_PLANES] = {(const v4 *)planes_device[0], (const v4 *)planes_device[1], (const v4 *)planes_device[2]};
+        return do_denoise(d, p, (const v4 *)beauty_device, planes, (v4 *)out_device, (hipStream_t)hip_stream, stats, 0);
+    });
+}
+
+int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixel *beauty, const PtrsFilmPixel *const planes[PTRS_AOV_PLANES], PtrsFilmPixel *out, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = dn_check_args(d, p, beauty, (const void *const *)planes, out);
+        if (rc != PTRS_OK || (rc = dn_select_device(d)) != PTRS_OK) return rc;
+        const auto t_begin = std::chrono::steady_clock::now();
+        const size_t bytes = (size_t)d->W * (size_t)d->H * sizeof(PtrsFilmPixel);
+        const PtrsFilmPixel *src[4] = {beauty, planes[0], planes[1], planes[2]};
+        for (int k = 0; k < 5; ++k) if ((rc = d->stage[k].ensure(bytes)) != PTRS_OK) return rc;
+        for (int k = 0; k < 4; ++k) HIPCHK(hipMemcpy(d->stage[k].p, src[k], bytes, hipMemcpyHostToDevice));
+        const v4 *pl[AOV_PLANES] = {(const v4 *)d->stage[1].p, (const v4 *)d->stage[2].p, (const v4 *)d->stage[3].p};
+        if ((rc = do_denoise(d, p, (const v4 *)d->stage[0].p, pl, (v4 *)d->stage[4].p, nullptr, stats, 5 * bytes)) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(out, d->stage[4].p, bytes, hipMemcpyDeviceToHost));
+        if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         return PTRS_OK;
     });
 }

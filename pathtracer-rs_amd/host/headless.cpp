@@ -25,7 +25,7 @@ static bool parse_resolution(const char *s, int &w, int &h) { // main.rs:23-33
 
 int main(int argc, char **argv) {
     std::string scene_path, out_dir, dump_path, dump_full_path, env_map_path;
-    bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false;
+    bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false, denoise = false;
     int n_gpus = 1;
     int spp = 1, max_depth = 15, w = 640, h = 480; // DEFAULT_RESOLUTION common/mod.rs:14
     bool have_out = false;
@@ -46,13 +46,14 @@ int main(int argc, char **argv) {
         else if (a == "--progress") progress = true;                   // a progress line per pass (the reference's progress bar, integrator.rs:631-634); like --preview it
                                                                        // renders through ptrs_render_progressive, which publishes the film after every pass (slower than the one-shot render)
         else if (a == "--aov") aov = true;                             // next to render.png: albedo.png, normal.png, depth.png (the first-hit planes of ptrs_render_aov, resolved)
+        else if (a == "--denoise") denoise = true;                     // next to render.png: denoised.png (ptrs_denoise on the film and the first-hit planes, default parameters)
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
         else scene_path = a;
     }
     if (scene_path.empty() || (!have_out && dump_path.empty() && dump_full_path.empty())) {
-        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--headless]\n");
+        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--headless]\n");
         return 2;
     }
     Camera camera; RenderScene scene; std::string err;
@@ -86,8 +87,8 @@ int main(int argc, char **argv) {
     const std::string out = out_dir + "/render.png"; // main.rs:70
     if (!write_png_rgba8(out, camera.film.width, camera.film.height, camera.film.to_rgba_image(), err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     std::fprintf(stderr, "INFO wrote %s\n", out.c_str());
+    std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES];
     if (aov) {
-        std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES];
         rc = integrator.render_aov(camera, scene, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, &st);
         if (rc != PTRS_OK) { std::fprintf(stderr, "error: aov render failed (%d): %s\n", rc, integrator.last_error.c_str()); return 1; }
         std::vector<uint8_t> img[PTRS_AOV_PLANES];
@@ -97,6 +98,13 @@ int main(int argc, char **argv) {
             if (!write_png_rgba8(out_dir + names[k], camera.film.width, camera.film.height, img[k], err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
             std::fprintf(stderr, "INFO wrote %s%s\n", out_dir.c_str(), names[k]);
         }
+    }
+    if (denoise) { // (the planes of --aov, when given, are the ones the filter is guided by)
+        Film dn(camera.film.width, camera.film.height);
+        rc = integrator.denoise(camera, scene, planes, dn.pixels, nullptr, &st);
+        if (rc != PTRS_OK) { std::fprintf(stderr, "error: denoise failed (%d): %s\n", rc, integrator.last_error.c_str()); return 1; }
+        if (!write_png_rgba8(out_dir + "/denoised.png", dn.width, dn.height, dn.to_rgba_image(), err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+        std::fprintf(stderr, "INFO wrote %s/denoised.png (%.3f ms, %llu launches)\n", out_dir.c_str(), st.ms_total, (unsigned long long)st.kernel_launches);
     }
     return 0;
 }

@@ -119,6 +119,24 @@ int PathIntegrator::render_aov(Camera &camera, RenderScene &scene, uint32_t plan
     if (rc != PTRS_OK) last_error = ptrs_last_error();
     return rc;
 }
+int PathIntegrator::denoise(Camera &camera, RenderScene &scene, std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<PtrsFilmPixel> &out, const PtrsDenoiseParams *dp, PtrsStats *stats) {
+    const size_t npx = (size_t)camera.film.width * (size_t)camera.film.height;
+    int rc;
+    if (planes[0].size() != npx || planes[1].size() != npx || planes[2].size() != npx) {
+        for (int k = 0; k < PTRS_AOV_PLANES; ++k) planes[k].clear();
+        if ((rc = render_aov(camera, scene, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, nullptr)) != PTRS_OK) return rc;
+    }
+    PtrsDenoiseParams p;
+    if (dp) p = *dp; else ptrs_denoise_default_params(&p);
+    PtrsDenoiser *d = nullptr;
+    if ((rc = ptrs_denoiser_create(device_, camera.film.width, camera.film.height, &d)) != PTRS_OK) { last_error = ptrs_last_error(); return rc; }
+    out.assign(npx, PtrsFilmPixel{{0, 0, 0}, 0});
+    const PtrsFilmPixel *ptrs[PTRS_AOV_PLANES] = {planes[0].data(), planes[1].data(), planes[2].data()};
+    rc = ptrs_denoise(d, &p, camera.film.pixels.data(), ptrs, out.data(), stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    ptrs_denoiser_destroy(d);
+    return rc;
+}
 void aov_to_rgba_images(int w, int h, const std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<uint8_t> rgba_out[PTRS_AOV_PLANES]) {
     const size_t npx = (size_t)w * (size_t)h;
     const std::vector<PtrsFilmPixel> &al = planes[0], &nr = planes[1], &dp = planes[2];

@@ -95,6 +95,10 @@ public:
     // ptrs_render_aov: the first-hit feature planes of the same view (plane k = bit k of `planes`: PTRS_AOV_ALBEDO | _NORMAL | _DEPTH),
     // accumulated into planes_inout[k] (resized to the film and cleared when its size does not fit).  max_depth plays no part.
     int render_aov(Camera &camera, RenderScene &scene, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats = nullptr);
+    // ptrs_denoise on camera.film and the three planes of render_aov (rendered here when `planes` does not hold them): the edge-avoiding
+    // a-trous filter of DESIGN 11 with `dp` (nullptr: ptrs_denoise_default_params).  camera.film keeps the noisy film; out receives
+    // width x height pixels, rgb = colour, weight = 1.
+    int denoise(Camera &camera, RenderScene &scene, std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<PtrsFilmPixel> &out, const PtrsDenoiseParams *dp = nullptr, PtrsStats *stats = nullptr);
     // When set, render() publishes the film after every pass of the pipeline (ptrs_render_progressive) and calls this with
     // (passes done, passes in total, first row, one past the last row that changed): the hook a preview gets instead of the
     // reference's second thread that reads the film every 2 s (headless.rs:197-214).

@@ -44,6 +44,8 @@ def load_library():
     for i, s in enumerate(structs):
         if L.ptrs_abi_sizeof(i) != C.sizeof(s):
             raise PtrsError("ABI struct %s: library %d bytes, binding %d bytes" % (s.__name__, L.ptrs_abi_sizeof(i), C.sizeof(s)))
+    if L.ptrs_abi_sizeof(11) != C.sizeof(abi.PtrsDenoiseParams):
+        raise PtrsError("ABI struct PtrsDenoiseParams: library %d bytes, binding %d bytes" % (L.ptrs_abi_sizeof(11), C.sizeof(abi.PtrsDenoiseParams)))
     L.ptrs_set_option.argtypes = [C.c_char_p, C.c_int64]
     L.ptrs_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.ptrs_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
@@ -260,6 +262,17 @@ class PathIntegrator:
         self.last_stats = stats
         return stats
 
+    def render_denoised(self, camera, scene, **params):
+        """render, then render_aov, then Denoiser.denoise (params: iterations, sigma_color, sigma_normal, sigma_depth, demodulate).  The
+        noisy film stays in camera.film; returns the denoised (H, W) FILM_DTYPE pixels (rgb = colour, weight = 1)."""
+        self.render(camera, scene)
+        planes = self.render_aov(camera, scene)
+        dn = Denoiser(camera.film.width, camera.film.height, self.device)
+        try:
+            return dn.denoise(camera.film.pixels, planes, **params)
+        finally:
+            dn.close()
+
     def render_progressive(self, camera, scene, on_pass, row_begin=0, row_end=0):
         """ptrs_render_progressive: like render(), and after every pass of the pipeline the rows it touched are copied into
         camera.film.pixels and on_pass(passes_done, passes_total, row_begin, row_end) is called (the preview hook the
@@ -313,6 +326,72 @@ class PathIntegrator:
         self.last_single_pixel_paths = round_up_pow2(p.spp)
         _check(load_library().ptrs_render_single_pixel(ds.handle, C.byref(cam), C.byref(p), int(pixel[0]), int(pixel[1]), C.c_void_p(out.ctypes.data)))
         return out
+
+
+def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, timing=False):
+    """PtrsDenoiseParams: ptrs_denoise_default_params (5 iterations, sigmas 0.25 / 0.3 / 0.1, demodulation on) with the given fields replaced."""
+    p = abi.PtrsDenoiseParams()
+    load_library().ptrs_denoise_default_params(C.byref(p))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if sigma_color is not None:
+        p.sigma_color = float(sigma_color)
+    if sigma_normal is not None:
+        p.sigma_normal = float(sigma_normal)
+    if sigma_depth is not None:
+        p.sigma_depth = float(sigma_depth)
+    if demodulate is not None:
+        p.flags = (p.flags & ~abi.PtrsDenoiseDemodulate) | (abi.PtrsDenoiseDemodulate if demodulate else 0)
+    if timing:  # the call's PtrsStats.debug then holds nanoseconds per launch: [0] prepare, [1 + i] iteration i, [9] finish
+        p.flags |= abi.PtrsDenoiseTiming
+    return p
+
+
+class Denoiser:
+    """PtrsDenoiser: the a-trous denoiser's workspace of one device for one width x height.  One call at a time."""
+
+    def __init__(self, width, height, device=0):
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        self.handle = C.c_void_p()
+        self.last_stats = None
+        _check(load_library().ptrs_denoiser_create(self.device, self.width, self.height, C.byref(self.handle)))
+
+    def denoise(self, film_pixels, planes, **params):
+        """ptrs_denoise: film_pixels (the beauty film) and planes["albedo" | "normal" | "depth"] (render_aov's dict), all (H, W)
+        FILM_DTYPE accumulated sums in host memory -> the denoised (H, W) FILM_DTYPE array (rgb = colour, weight = 1; zeros where the
+        beauty film has no weight).  The inputs are not written."""
+        films = [film_pixels] + [planes[k] for k in abi.PtrsAovNames]
+        for f in films:
+            if f.dtype != abi.FILM_DTYPE or f.shape != (self.height, self.width) or not f.flags.c_contiguous:
+                raise PtrsError("denoise: every film must be a contiguous (%d, %d) FILM_DTYPE array" % (self.height, self.width))
+        out = np.zeros((self.height, self.width), dtype=abi.FILM_DTYPE)
+        p = denoise_params(**params)
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)(*[f.ctypes.data for f in films[1:]])
+        stats = abi.PtrsStats()
+        _check(load_library().ptrs_denoise(self.handle, C.byref(p), C.c_void_p(films[0].ctypes.data), ptrs, C.c_void_p(out.ctypes.data), C.byref(stats)))
+        self.last_stats = stats
+        return out
+
+    def denoise_device(self, beauty_device_ptr, plane_device_ptrs, out_device_ptr, stream=0, **params):
+        """ptrs_denoise_device: the films in device memory (width*height*16 bytes each; plane_device_ptrs maps a plane's name to its
+        address), the work queued on `stream`; returns the call's PtrsStats after the stream has drained."""
+        p = denoise_params(**params)
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)(*[int(plane_device_ptrs[k]) for k in abi.PtrsAovNames])
+        stats = abi.PtrsStats()
+        _check(load_library().ptrs_denoise_device(self.handle, C.byref(p), C.c_void_p(int(beauty_device_ptr)), ptrs, C.c_void_p(int(out_device_ptr)), C.c_void_p(int(stream)), C.byref(stats)))
+        self.last_stats = stats
+        return stats
+
+    def close(self):
+        if self.handle:
+            load_library().ptrs_denoiser_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _aov_mask(planes):
