@@ -362,6 +362,65 @@ int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixe
 int ptrs_denoise_device(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty_device,
                         const void *const planes_device[PTRS_AOV_PLANES], void *out_device, void *hip_stream, PtrsStats *stats);
 
+/* Sample ranges, the film's error and rendering until it has converged (no counterpart in the reference, which renders a fixed spp;
+ * the contracts are DESIGN.md section 12).
+ *
+ * ptrs_render_range: samples [sample_begin, sample_end) of `params`' render -- params->spp stays the WHOLE render's count (rounded up
+ * to a power of two as always; the stratified sampler takes it as is) -- accumulated into film_inout like ptrs_render, and, when
+ * film_half_inout is given (it must not be film_inout), into that film as well by a second gather of the same passes.  Refused with
+ * PTRS_ERR_INVALID before any device call unless sample_begin < sample_end <= the rounded spp.  row_begin / row_end as in ptrs_render.
+ * sample_rgb (may be NULL) has ptrs_render_samples' layout with the absolute sample number; only the range's entries are written.
+ * stats are those of the range.  With a pass plan that keeps the band's rows in one pass, successive ranges that tile [0, spp) give
+ * ptrs_render's film bit for bit.  The _device form takes the films in device memory and a stream. */
+int ptrs_render_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                      PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats);
+int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                             void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats);
+
+/* ptrs_film_error: how far a film is from the film of half of its samples (the half-buffer measure of Dammertz et al.'s stopping
+ * condition), per 16 x 16 tile (clipped at the right and bottom edges; tile index = ty * tiles_x + tx) and for the whole film.
+ * Per pixel, in binary32: valid = both weights > 0; I = film.rgb / film.weight, A = half.rgb / half.weight,
+ * e = ((|I.r - A.r| + |I.g - A.g|) + |I.b - A.b|) / sqrt(max((I.r + I.g) + I.b, 1e-3)), a NaN or infinite e becomes +inf; an invalid
+ * pixel has e = 0 and is not counted.  Per tile: error = the sum of e (stride-halving tree over the tile's 256 slots) / valid, 0 for a
+ * tile without a valid pixel.  Summary: the largest tile error, the lowest tile index that has it, the valid pixels of the film.
+ * The films are never written; film and half must differ.  The argument checks are made before the first device call.  The _device
+ * form takes device pointers (tiles_out_device is required: tiles_x * tiles_y records) and a stream; summary_out is host memory. */
+typedef struct PtrsTileError { float error; uint32_t valid; } PtrsTileError;
+typedef struct PtrsFilmErrorSummary {
+    float max_tile_error;
+    uint32_t worst_tile;
+    uint64_t valid_pixels;
+    uint32_t tiles_x, tiles_y;
+} PtrsFilmErrorSummary;
+#define PTRS_ERROR_TILE 16
+int ptrs_film_error(int32_t device, int32_t width, int32_t height, const PtrsFilmPixel *film, const PtrsFilmPixel *half,
+                    PtrsTileError *tiles_out /* may be NULL */, PtrsFilmErrorSummary *summary_out);
+int ptrs_film_error_device(int32_t device, int32_t width, int32_t height, const void *film_device, const void *half_device,
+                           void *tiles_out_device, void *hip_stream, PtrsFilmErrorSummary *summary_out);
+
+/* Render until converged.  params->spp is the ceiling, min_spp a power of two in 2 .. spp, target_error finite and >= 0.  The schedule
+ * (ptrs_converge_schedule, a pure function): block 0 is [0, min_spp), block k is [n, 2n) with n the samples before it; the first half
+ * of every block goes to the film and the half film, the second half to the film only, so the half film always holds n / 2 of the n
+ * samples; behind every block ptrs_film_error is asked, and the render stops when max_tile_error < target_error or n = spp.  The two
+ * films stay on the device, only the summary crosses to the host per check.  film_inout (host) ACCUMULATES like ptrs_render (the
+ * measure means what it says for a film that starts cleared); film_half_out (may be NULL) receives the half film.  history_out: one
+ * record per check, at most PTRS_CONVERGE_MAX_CHECKS.  stats (may be NULL): samples, rays, passes and launches summed over the blocks.
+ * The film after stopping at n is the film of ptrs_render_range(0, n); at n = spp it is ptrs_render's, bit for bit. */
+#define PTRS_CONVERGE_MAX_CHECKS 32
+typedef struct PtrsConvergeCheck { uint32_t spp; float max_tile_error; } PtrsConvergeCheck;
+typedef struct PtrsConvergeResult {
+    uint32_t spp_done;
+    uint32_t converged; /* 1: the last check was below the target */
+    uint32_t n_checks;
+    uint32_t worst_tile; /* of the last check */
+    PtrsConvergeCheck history[PTRS_CONVERGE_MAX_CHECKS];
+} PtrsConvergeResult;
+/* blocks_out: 3 numbers per block -- begin, middle, end: [begin, middle) goes to both films, [middle, end) to the film only; at most
+ * PTRS_CONVERGE_MAX_CHECKS blocks.  Refuses (PTRS_ERR_INVALID) an spp or min_spp that is no power of two, or min_spp outside 2 .. spp. */
+int ptrs_converge_schedule(uint32_t spp, uint32_t min_spp, uint32_t *blocks_out, uint32_t *n_blocks_out);
+int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
+                          PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, PtrsConvergeResult *result_out, PtrsStats *stats);
+
 /* PathIntegrator::render_single_pixel (integrator.rs:505-534): radiance of every sample of one
  * pixel, rgb_out[spp*3]. */
 int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera,

@@ -102,8 +102,29 @@ class PtrsDenoiseParams(C.Structure):
 
 PtrsDenoiseDemodulate, PtrsDenoiseTiming, PtrsDenoiseMaxIterations = 1, 2, 8
 
+
+class PtrsTileError(C.Structure):  # ptrs_film_error: one 16 x 16 tile
+    _fields_ = [("error", C.c_float), ("valid", C.c_uint32)]
+
+
+class PtrsFilmErrorSummary(C.Structure):
+    _fields_ = [("max_tile_error", C.c_float), ("worst_tile", C.c_uint32), ("valid_pixels", C.c_uint64), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32)]
+
+
+PtrsErrorTile, PtrsConvergeMaxChecks = 16, 32
+
+
+class PtrsConvergeCheck(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("max_tile_error", C.c_float)]
+
+
+class PtrsConvergeResult(C.Structure):  # ptrs_render_converged
+    _fields_ = [("spp_done", C.c_uint32), ("converged", C.c_uint32), ("n_checks", C.c_uint32), ("worst_tile", C.c_uint32), ("history", PtrsConvergeCheck * PtrsConvergeMaxChecks)]
+
+
 HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4")])
 FILM_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4")])
+TILE_DTYPE = np.dtype([("error", "<f4"), ("valid", "<u4")])
 
 
 def _f32(a):

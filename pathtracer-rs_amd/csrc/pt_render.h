@@ -139,6 +139,14 @@ inline void plan_bands(int32_t height, uint32_t n, const float *row_cost, int32_
     }
 }
 
+// The sample count render_impl makes of prm.spp (Sobol: rounded up to a power of two; stratified: as given), and ptrs_render_range's
+// check of its range against it -- made by the entry points before their first device call.
+inline uint32_t total_spp(const PtrsRenderParams &prm) {
+    if (prm.sampler == PTRS_SAMPLER_STRATIFIED) return (uint32_t)(prm.spp < 1 ? 1 : prm.spp);
+    return (uint32_t)round_up_pow2_i64((int64_t)(prm.spp < 1 ? 1 : prm.spp));
+}
+inline bool sample_range_ok(const PtrsRenderParams &prm, uint32_t sample_begin, uint32_t sample_end) { return prm.spp > 0 && sample_begin < sample_end && sample_end <= total_spp(prm); }
+
 struct RenderProgress { void (*fn)(void *user, uint32_t done, uint32_t total, int32_t row_begin, int32_t row_end); void *user; };
 // ptrs_render_dump_rays: the render stops in its first pass before round `round` and hands out the extension rays of that round
 // (round 0: the camera rays; round k: the rays leaving the paths' k-th vertices) -- ray sets of a real frame for the traversal bench.
@@ -151,7 +159,10 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
                 const RayDump *dump = nullptr,
                 const int32_t *single_pixel = nullptr /* render_single_pixel (integrator.rs:505-534): raster (px, py), any pixel of the sample bounds;
                                                          traces that pixel's spp paths only, no film, samples_out = spp * 3 floats */,
-                uint32_t *row_cost = nullptr /* backend memory, NY counters (zeroed by the caller): the BVH queries of every sample row's paths are added; no film */) {
+                uint32_t *row_cost = nullptr /* backend memory, NY counters (zeroed by the caller): the BVH queries of every sample row's paths are added; no film */,
+                const uint32_t *sample_range = nullptr /* ptrs_render_range: {begin, end}, samples [begin, end) of the spp-sample render (null: all of them).  The passes run
+                                                          over the range; the sampler, the sample layout and the ray differentials stay those of the whole render */,
+                v4 *film_half = nullptr /* backend memory, W*H: a second film that receives the same samples (a second gather of every pass, chained in the same order) */) {
     using clock = std::chrono::steady_clock;
     const bool *kinds_present = sc_host_feat.kinds_present;
     auto t_begin = clock::now();
@@ -169,6 +180,10 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
         if (single_pixel) { err = "render_single_pixel with the stratified sampler is not supported (its tables depend on the tile's earlier pixels)"; return PTRS_ERR_UNSUPPORTED; }
         g.spp = strat_dim * strat_dim;
     } else if (prm.sampler != PTRS_SAMPLER_SOBOL) { err = "unknown sampler"; return PTRS_ERR_INVALID; }
+    const uint32_t sb = sample_range ? sample_range[0] : 0u, se = sample_range ? sample_range[1] : g.spp; // the samples this call traces
+    if (!(sb < se && se <= g.spp)) { err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(g.spp) + " for these parameters)"; return PTRS_ERR_INVALID; }
+    if (film_half && film_half == film) { err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
+    const uint32_t ns = se - sb;
     if (g.log2_res < 1 || g.log2_res > 25 || 2u * g.log2_res + (31u - (uint32_t)__builtin_clz(g.spp)) > 62u) { err = "resolution / spp outside the Sobol index range"; return PTRS_ERR_UNSUPPORTED; }
     int32_t rb = prm.row_begin, re = prm.row_end;
     if (re <= rb) { rb = 0; re = prm.height; }
@@ -207,20 +222,20 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     // tail of a kernel or waits for its next launch, the other pass's workgroups fill the machine (two concurrent
     // processes on one MI355X measured +18 % over one).  Film kernels are chained in pass order, so the film is formed
     // by exactly the same additions as with a single pipeline.
-    const uint32_t n_lanes = std::max(1u, be.lanes((uint64_t)(srow1 - srow0) * (uint64_t)g.NX * (uint64_t)g.spp, sc_host_feat.kinds_present, single_pixel != nullptr, g.spp)); // (the back end may choose by the size of the job)
+    const uint32_t n_lanes = std::max(1u, be.lanes((uint64_t)(srow1 - srow0) * (uint64_t)g.NX * (uint64_t)ns, sc_host_feat.kinds_present, single_pixel != nullptr, ns)); // (the back end may choose by the size of the job: a range's job is its own samples)
     // up to 2^27 paths (~35 GB of path state) per lane: HBM (288 GB) is plentiful, launches and tails are not free.  The back
     // end bounds it by its share of the memory that is free right now, so the library stays embeddable beside other users.
     uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, sc_host_feat.kinds_present)); // (2^27: a path slot is 27 bits of a NEE-queue entry, pt_scene.h)
     if (capacity < (uint64_t)g.NX) capacity = (uint64_t)g.NX;
-    if (single_pixel) capacity = std::max<uint64_t>(capacity, (uint64_t)g.NX * g.spp); // one pass: the pixel's spp paths (planned below as one row x all samples, launched as spp paths)
+    if (single_pixel) capacity = std::max<uint64_t>(capacity, (uint64_t)g.NX * ns); // one pass: the pixel's spp paths (planned below as one row x all samples, launched as spp paths)
     const uint64_t band_rows = (uint64_t)(srow1 - srow0);
     uint64_t rows_per_pass, samples_per_pass;
     if (band_rows * (uint64_t)g.NX <= capacity) {
         rows_per_pass = band_rows;
         // balance the sample chunks: n passes of (almost) equal size instead of full passes plus a small tail
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
-        const uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
-        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
+        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(ns, capacity / (band_rows * (uint64_t)g.NX)));
+        const uint64_t n_chunks = (ns + spp_max - 1) / spp_max;
+        samples_per_pass = (ns + n_chunks - 1) / n_chunks;
     } else {
         samples_per_pass = 1;
         const uint64_t rows_max = std::max<uint64_t>(1, capacity / (uint64_t)g.NX);
@@ -228,10 +243,10 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
         rows_per_pass = (band_rows + n_chunks - 1) / n_chunks;
     }
     if (n_lanes > 1 && band_rows * (uint64_t)g.NX <= capacity && !prm.paths_per_pass) { // an even number of equal sample chunks
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
-        uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
-        if (g.spp >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes;
-        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
+        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(ns, capacity / (band_rows * (uint64_t)g.NX)));
+        uint64_t n_chunks = (ns + spp_max - 1) / spp_max;
+        if (ns >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes;
+        samples_per_pass = (ns + n_chunks - 1) / n_chunks;
     }
     const uint64_t max_paths = rows_per_pass * (uint64_t)g.NX * samples_per_pass;
     if (max_paths >= 0xffffffffull) { err = "pass too large"; return PTRS_ERR_INVALID; }
@@ -245,7 +260,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     PtrsStats st;
     std::memset(&st, 0, sizeof(st));
     std::vector<uint32_t> counts((size_t)(max_iters + 1u) * Q_STRIDE);
-    const uint32_t n_passes_total = (uint32_t)(((band_rows + rows_per_pass - 1) / rows_per_pass) * ((g.spp + samples_per_pass - 1) / samples_per_pass));
+    const uint32_t n_passes_total = (uint32_t)(((band_rows + rows_per_pass - 1) / rows_per_pass) * ((ns + samples_per_pass - 1) / samples_per_pass));
     struct Pending { bool active = false, open = false; uint32_t it = 0, n_paths = 0, pass_no = 0; int32_t y0 = 0, y1 = 0; };
     std::vector<Pending> pending(n_lanes);
     bool null_skip_overrun = false;
@@ -272,6 +287,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
         }
         pd.it = it;
         if (pd.y1 > pd.y0 && film) be.film(film, pd.y0, pd.y1); // ordered after the previous pass's film kernel, whichever lane ran it
+        if (pd.y1 > pd.y0 && film_half) be.film(film_half, pd.y0, pd.y1); // (the same pass into the half film: its own running sums, in the same order)
         if (samples_out) be.export_samples(samples_out);
         pd.open = false;
     };
@@ -298,8 +314,8 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     uint32_t pass_no = 0;
     for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass) {
         const int32_t r1 = std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass);
-        for (uint32_t s0 = 0; s0 < g.spp; s0 += (uint32_t)samples_per_pass, ++pass_no) {
-            const uint32_t s1 = (uint32_t)std::min<uint64_t>(g.spp, (uint64_t)s0 + samples_per_pass);
+        for (uint32_t s0 = sb; s0 < se; s0 += (uint32_t)samples_per_pass, ++pass_no) {
+            const uint32_t s1 = (uint32_t)std::min<uint64_t>(se, (uint64_t)s0 + samples_per_pass);
             const uint32_t lane = pass_no % n_lanes;
             // (an open pass is closed -- asked for more rounds, its film kernel enqueued -- when its lane comes round again: passes close in pass
             // order, the order their film kernels are chained in)

@@ -24,6 +24,7 @@
 #include "pt_render.h"
 #include "pt_aov.h"
 #include "pt_denoise.h"
+#include "pt_converge.h"
 #include "pt_probe.h"
 
 using namespace pt;
@@ -1382,6 +1383,51 @@ __global__ __launch_bounds__(BLOCK) void k_dn_finish(uint32_t n, const v4 *__res
     if (i < n) out[i] = dn_finish(x[i], a[i]);
 }
 
+// ---- the film's error against its half film (pt_converge.h) ----------------------------------------------------------
+// One workgroup per 16 x 16 tile, one thread per pixel: 32 bytes read per pixel, 8 written per tile.  The 256 errors are summed by the
+// stride-halving tree of cv_tile_sum: strides 128 and 64 through LDS, the last six across the lanes of wave 0 (lane i takes lane
+// i + off's value: for i < off that is v[i] += v[i + off]; what the lanes beyond off make of it is never read again).  The valid
+// counts ride along as integers.  A pixel beyond the image is an empty slot and is never loaded.
+__global__ __launch_bounds__(BLOCK) void k_film_error(int32_t W, int32_t H, int32_t tiles_x, const v4 *__restrict__ film, const v4 *__restrict__ half, PtrsTileError *__restrict__ tiles) {
+    static_assert(BLOCK == CV_SLOTS, "one thread per slot of a tile");
+    __shared__ float v[CV_SLOTS]; __shared__ uint32_t c[CV_SLOTS];
+    const uint32_t t = threadIdx.x;
+    const int32_t x = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * CV_TILE + (int32_t)(t & 15u), y = (int32_t)(blockIdx.x / (uint32_t)tiles_x) * CV_TILE + (int32_t)(t >> 4);
+    CvPixel p; p.e = 0.0f; p.valid = 0u;
+    if (x < W && y < H) { const size_t q = (size_t)y * (size_t)W + (size_t)x; p = cv_pixel(film[q], half[q]); }
+    v[t] = p.e; c[t] = p.valid;
+    __syncthreads();
+    if (t < 128u) { v[t] = v[t] + v[t + 128u]; c[t] += c[t + 128u]; }
+    __syncthreads();
+    if (t < 64u) {
+        float e = v[t] + v[t + 64u]; uint32_t n = c[t] + c[t + 64u];
+        for (int off = 32; off > 0; off >>= 1) { e = e + __shfl_down(e, off); n += (uint32_t)__shfl_down((int)n, off); }
+        if (t == 0u) tiles[blockIdx.x] = cv_tile(e, n);
+    }
+}
+
+// The tile records -> the summary, one workgroup: every thread keeps the best of its tiles (cv_better: larger error, then lower index)
+// and their valid pixels, then a tree over the 256 candidates.  Maximum and integer sum do not depend on the order.
+__global__ __launch_bounds__(BLOCK) void k_film_error_summary(const PtrsTileError *__restrict__ tiles, uint32_t n_tiles, uint32_t tiles_x, uint32_t tiles_y, PtrsFilmErrorSummary *__restrict__ out) {
+    __shared__ float se[BLOCK]; __shared__ uint32_t si[BLOCK]; __shared__ unsigned long long sn[BLOCK];
+    const uint32_t t = threadIdx.x;
+    float e = -1.0f; uint32_t idx = 0xffffffffu; unsigned long long n = 0ull; // (any tile beats the start: tile errors are >= 0)
+    for (uint32_t i = t; i < n_tiles; i += BLOCK) {
+        const PtrsTileError T = tiles[i];
+        if (cv_better(T.error, i, e, idx)) { e = T.error; idx = i; }
+        n += T.valid;
+    }
+    se[t] = e; si[t] = idx; sn[t] = n;
+    for (uint32_t off = BLOCK / 2u; off > 0u; off >>= 1) {
+        __syncthreads();
+        if (t < off) {
+            if (cv_better(se[t + off], si[t + off], se[t], si[t])) { se[t] = se[t + off]; si[t] = si[t + off]; }
+            sn[t] += sn[t + off];
+        }
+    }
+    if (t == 0u) { PtrsFilmErrorSummary s; s.max_tile_error = se[0]; s.worst_tile = si[0]; s.valid_pixels = sn[0]; s.tiles_x = tiles_x; s.tiles_y = tiles_y; *out = s; }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -1559,6 +1605,7 @@ struct PtrsScene {
     DevBuf ws[MAX_LANES][32];   // per pipeline lane
     DevBuf counts[MAX_LANES], totals[MAX_LANES], tickets[MAX_LANES];
     DevBuf stats, table, film_tmp, samples_tmp, strat1, strat2, row_cost;
+    DevBuf half_tmp, cv_tiles, cv_summary; // ptrs_render_range / ptrs_render_converged: the half film, the tile records and the summary of the error checks
     DevBuf aov_film_tmp[AOV_PLANES], aov_samples_tmp; // ptrs_render_aov: the host planes' device copies, the per-sample export
     DevBuf aov_band[4], aov_band_pfilm;               // ptrs_render_aov in band mode (pt_aov.h): the values and p_film of one sample index of the whole band
     hipStream_t lane_stream[MAX_LANES] = {}; // lane 0 runs on the caller's stream, the others on these
@@ -1566,7 +1613,7 @@ struct PtrsScene {
     std::vector<hipEvent_t> ev_pool;
     int n_cu = 256;
     ~PtrsScene() {
-        for (auto &b : {&stack_spill, &nodes2, &nodes4, &nodes, &tris, &shade, &mats, &texs, &levels, &texdata, &lights, &distdata, &inf, &stats, &table, &film_tmp, &samples_tmp, &strat1, &strat2, &row_cost}) b->release();
+        for (auto &b : {&stack_spill, &nodes2, &nodes4, &nodes, &tris, &shade, &mats, &texs, &levels, &texdata, &lights, &distdata, &inf, &stats, &table, &film_tmp, &samples_tmp, &strat1, &strat2, &row_cost, &half_tmp, &cv_tiles, &cv_summary}) b->release();
         for (auto &b : aov_film_tmp) b.release();
         for (auto &b : aov_band) b.release();
         aov_band_pfilm.release();
@@ -2059,7 +2106,8 @@ Options scene_options(const PtrsScene *ps) { // the process-wide knobs with this
 }
 
 int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, v4 *film_dev, float *samples_dev, hipStream_t stream, PtrsStats *stats, const int32_t *single_pixel = nullptr,
-              const RenderProgress *progress = nullptr, PtrsFilmPixel *host_film = nullptr, int share = 1, const RayDump *dump = nullptr, uint32_t *row_cost_dev = nullptr) {
+              const RenderProgress *progress = nullptr, PtrsFilmPixel *host_film = nullptr, int share = 1, const RayDump *dump = nullptr, uint32_t *row_cost_dev = nullptr,
+              const uint32_t *sample_range = nullptr, v4 *film_half_dev = nullptr) {
     if (!ps || !cam || !prm || (!film_dev && !single_pixel && !row_cost_dev)) { g_err = "null argument"; return PTRS_ERR_INVALID; }
     HIPCHK(hipSetDevice(ps->device));
     HipBackend be;
@@ -2068,7 +2116,7 @@ int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm,
     int rc = get_sobol(ps->device, &be.sob);
     if (rc != PTRS_OK) return rc;
     std::string err;
-    rc = render_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, film_dev, samples_dev, stats, err, progress, dump, single_pixel, row_cost_dev);
+    rc = render_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, film_dev, samples_dev, stats, err, progress, dump, single_pixel, row_cost_dev, sample_range, film_half_dev);
     if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
     if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
     return PTRS_OK;
@@ -2095,6 +2143,38 @@ int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *
     rc = render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err);
     if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
     if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
+    return PTRS_OK;
+}
+
+// The error of a device film against its half film: tile records into tiles_dev, the summary through sum_dev into host memory; on
+// `stream`, returns with the stream drained.  (The callers have made cv_check_args' checks and selected the device.)
+int do_film_error(int32_t W, int32_t H, const v4 *film, const v4 *half, PtrsTileError *tiles_dev, PtrsFilmErrorSummary *sum_dev, hipStream_t stream, PtrsFilmErrorSummary *summary_out) {
+    const uint32_t tiles_x = ((uint32_t)W + CV_TILE - 1u) / CV_TILE, tiles_y = ((uint32_t)H + CV_TILE - 1u) / CV_TILE, n_tiles = tiles_x * tiles_y;
+    hipLaunchKernelGGL(k_film_error, dim3(n_tiles), dim3(BLOCK), 0, stream, W, H, (int32_t)tiles_x, film, half, tiles_dev);
+    hipLaunchKernelGGL(k_film_error_summary, dim3(1), dim3(BLOCK), 0, stream, (const PtrsTileError *)tiles_dev, n_tiles, tiles_x, tiles_y, sum_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(summary_out, sum_dev, sizeof(PtrsFilmErrorSummary), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return PTRS_OK;
+}
+int cv_select_device(int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    return PTRS_OK;
+}
+// ptrs_render_range / ptrs_render_range_device / ptrs_render_converged: the checks that need no device, then that there is one
+int range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *film, const void *half) {
+    if (!scene || !camera || !params || !film) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
+    if (half && half == film) { g_err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
+    int32_t rb = params->row_begin, re = params->row_end;
+    if (re <= rb) { rb = 0; re = params->height; }
+    if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
     return PTRS_OK;
 }
 
@@ -2196,6 +2276,7 @@ int ptrs_abi_sizeof(int which) {
         case 3: return (int)sizeof(PtrsLight); case 4: return (int)sizeof(PtrsBvhNode); case 5: return (int)sizeof(PtrsSceneDesc);
         case 6: return (int)sizeof(PtrsCamera); case 7: return (int)sizeof(PtrsRenderParams); case 8: return (int)sizeof(PtrsStats);
         case 9: return (int)sizeof(PtrsHit); case 10: return (int)sizeof(PtrsFilmPixel); case 11: return (int)sizeof(PtrsDenoiseParams);
+        case 12: return (int)sizeof(PtrsTileError); case 13: return (int)sizeof(PtrsFilmErrorSummary); case 14: return (int)sizeof(PtrsConvergeResult);
         default: return -1;
     }
 }
@@ -2408,6 +2489,147 @@ int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixe
         if ((rc = do_denoise(d, p, (const v4 *)d->stage[0].p, pl, (v4 *)d->stage[4].p, nullptr, stats, 5 * bytes)) != PTRS_OK) return rc;
         HIPCHK(hipMemcpy(out, d->stage[4].p, bytes, hipMemcpyDeviceToHost));
         if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        return PTRS_OK;
+    });
+}
+
+// ---- sample ranges, the film's error, render until converged ------------------------------------------------------
+int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                             void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout_device, film_half_inout_device);
+        if (rc != PTRS_OK) return rc;
+        const uint32_t range[2] = {sample_begin, sample_end};
+        return do_render(scene, camera, params, (v4 *)film_inout_device, nullptr, (hipStream_t)hip_stream, stats, nullptr, nullptr, nullptr, 1, nullptr, nullptr, range, (v4 *)film_half_inout_device);
+    });
+}
+
+int ptrs_render_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                      PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout, film_half_inout);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipSetDevice(scene->device));
+        // only the rows of the band travel, like ptrs_render_samples
+        int32_t rb = params->row_begin, re = params->row_end;
+        if (re <= rb) { rb = 0; re = params->height; }
+        const size_t npx = (size_t)params->width * (size_t)params->height;
+        const size_t band_off = (size_t)rb * (size_t)params->width, band_bytes = (size_t)(re - rb) * (size_t)params->width * sizeof(PtrsFilmPixel);
+        if ((rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->film_tmp.p + band_off, film_inout + band_off, band_bytes, hipMemcpyHostToDevice));
+        if (film_half_inout) {
+            if ((rc = scene->half_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
+            HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->half_tmp.p + band_off, film_half_inout + band_off, band_bytes, hipMemcpyHostToDevice));
+        }
+        float *sdev = nullptr; size_t sbytes = 0;
+        if (sample_rgb) { // the caller's buffer travels there and back: the entries outside the range keep what they held
+            const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
+            sbytes = (size_t)g.NX * (size_t)g.NY * (size_t)total_spp(*params) * 3 * sizeof(float);
+            if ((rc = scene->samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
+            HIPCHK(hipMemcpy(scene->samples_tmp.p, sample_rgb, sbytes, hipMemcpyHostToDevice));
+            sdev = (float *)scene->samples_tmp.p;
+        }
+        const uint32_t range[2] = {sample_begin, sample_end};
+        rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, sdev, nullptr, stats, nullptr, nullptr, nullptr, 1, nullptr, nullptr, range, film_half_inout ? (v4 *)scene->half_tmp.p : nullptr);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(film_inout + band_off, (PtrsFilmPixel *)scene->film_tmp.p + band_off, band_bytes, hipMemcpyDeviceToHost));
+        if (film_half_inout) HIPCHK(hipMemcpy(film_half_inout + band_off, (PtrsFilmPixel *)scene->half_tmp.p + band_off, band_bytes, hipMemcpyDeviceToHost));
+        if (sample_rgb) HIPCHK(hipMemcpy(sample_rgb, sdev, sbytes, hipMemcpyDeviceToHost));
+        return PTRS_OK;
+    });
+}
+
+int ptrs_film_error_device(int32_t device, int32_t width, int32_t height, const void *film_device, const void *half_device, void *tiles_out_device, void *hip_stream, PtrsFilmErrorSummary *summary_out) {
+    return guarded([&]() -> int {
+        if (const char *m = cv_check_args(width, height, film_device, half_device, summary_out)) { g_err = m; return PTRS_ERR_INVALID; }
+        if (!tiles_out_device) { g_err = "null argument (the device form needs tiles_out_device)"; return PTRS_ERR_INVALID; }
+        int rc = cv_select_device(device);
+        if (rc != PTRS_OK) return rc;
+        DevBuf sum; // (a handle-free call owns nothing between calls: 24 bytes for the summary's way to the host)
+        if ((rc = sum.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
+        rc = do_film_error(width, height, (const v4 *)film_device, (const v4 *)half_device, (PtrsTileError *)tiles_out_device, (PtrsFilmErrorSummary *)sum.p, (hipStream_t)hip_stream, summary_out);
+        if (rc != PTRS_OK) (void)hipStreamSynchronize((hipStream_t)hip_stream);
+        sum.release();
+        return rc;
+    });
+}
+
+int ptrs_film_error(int32_t device, int32_t width, int32_t height, const PtrsFilmPixel *film, const PtrsFilmPixel *half, PtrsTileError *tiles_out, PtrsFilmErrorSummary *summary_out) {
+    return guarded([&]() -> int {
+        if (const char *m = cv_check_args(width, height, film, half, summary_out)) { g_err = m; return PTRS_ERR_INVALID; }
+        int rc = cv_select_device(device);
+        if (rc != PTRS_OK) return rc;
+        const size_t bytes = (size_t)width * (size_t)height * sizeof(PtrsFilmPixel);
+        const size_t n_tiles = (size_t)(((uint32_t)width + CV_TILE - 1u) / CV_TILE) * (size_t)(((uint32_t)height + CV_TILE - 1u) / CV_TILE);
+        DevBuf f, h, t, sum;
+        auto work = [&]() -> int {
+            int r;
+            if ((r = f.ensure(bytes)) != PTRS_OK || (r = h.ensure(bytes)) != PTRS_OK || (r = t.ensure(n_tiles * sizeof(PtrsTileError))) != PTRS_OK || (r = sum.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return r;
+            HIPCHK(hipMemcpy(f.p, film, bytes, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(h.p, half, bytes, hipMemcpyHostToDevice));
+            if ((r = do_film_error(width, height, (const v4 *)f.p, (const v4 *)h.p, (PtrsTileError *)t.p, (PtrsFilmErrorSummary *)sum.p, nullptr, summary_out)) != PTRS_OK) return r;
+            if (tiles_out) HIPCHK(hipMemcpy(tiles_out, t.p, n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost));
+            return PTRS_OK;
+        };
+        rc = work();
+        if (rc != PTRS_OK) (void)hipDeviceSynchronize();
+        f.release(); h.release(); t.release(); sum.release();
+        return rc;
+    });
+}
+
+int ptrs_converge_schedule(uint32_t spp, uint32_t min_spp, uint32_t *blocks_out, uint32_t *n_blocks_out) {
+    if (const char *m = cv_schedule(spp, min_spp, blocks_out, n_blocks_out)) { g_err = m; return PTRS_ERR_INVALID; }
+    return PTRS_OK;
+}
+
+int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
+                          PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, PtrsConvergeResult *result_out, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        if (!result_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (!(target_error >= 0.0f && target_error < PT_INF)) { g_err = "render_converged: target_error must be finite and >= 0"; return PTRS_ERR_INVALID; }
+        uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
+        if (!scene || !camera || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+        if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
+        if (params->width > 0 && params->height > 0 && (uint64_t)params->width * (uint64_t)params->height >= (1ull << 31)) { g_err = "film too large for the error measure"; return PTRS_ERR_INVALID; }
+        if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_converged renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+        int rc = range_check_args(scene, camera, params, 0u, min_spp, film_inout, film_half_out);
+        if (rc != PTRS_OK) return rc;
+        const auto t_begin = std::chrono::steady_clock::now();
+        HIPCHK(hipSetDevice(scene->device));
+        const int32_t W = params->width, H = params->height;
+        const size_t bytes = (size_t)W * (size_t)H * sizeof(PtrsFilmPixel);
+        const size_t n_tiles = (size_t)(((uint32_t)W + CV_TILE - 1u) / CV_TILE) * (size_t)(((uint32_t)H + CV_TILE - 1u) / CV_TILE);
+        if ((rc = scene->film_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->half_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->cv_tiles.ensure(n_tiles * sizeof(PtrsTileError))) != PTRS_OK ||
+            (rc = scene->cv_summary.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(scene->film_tmp.p, film_inout, bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(scene->half_tmp.p, 0, bytes));
+        PtrsConvergeResult res; std::memset(&res, 0, sizeof(res));
+        PtrsStats total; std::memset(&total, 0, sizeof(total));
+        for (uint32_t k = 0; k < n_blocks; ++k) {
+            const uint32_t parts[2][2] = {{blocks[3 * k], blocks[3 * k + 1]}, {blocks[3 * k + 1], blocks[3 * k + 2]}};
+            for (int h = 0; h < 2; ++h) { // the block's first half into both films, its second half into the film only
+                PtrsStats st;
+                if ((rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, nullptr, nullptr, &st, nullptr, nullptr, nullptr, 1, nullptr, nullptr, parts[h], h == 0 ? (v4 *)scene->half_tmp.p : nullptr)) != PTRS_OK) return rc;
+                total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
+                total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
+                total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
+            }
+            PtrsFilmErrorSummary sum;
+            if ((rc = do_film_error(W, H, (const v4 *)scene->film_tmp.p, (const v4 *)scene->half_tmp.p, (PtrsTileError *)scene->cv_tiles.p, (PtrsFilmErrorSummary *)scene->cv_summary.p, nullptr, &sum)) != PTRS_OK) return rc;
+            total.kernel_launches += 2;
+            res.spp_done = blocks[3 * k + 2];
+            res.history[res.n_checks].spp = res.spp_done; res.history[res.n_checks].max_tile_error = sum.max_tile_error; ++res.n_checks;
+            res.worst_tile = sum.worst_tile;
+            res.converged = sum.max_tile_error < target_error ? 1u : 0u;
+            if (res.converged) break;
+        }
+        HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
+        if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
+        *result_out = res;
+        total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if (stats) *stats = total;
         return PTRS_OK;
     });
 }

@@ -27,6 +27,7 @@ int main(int argc, char **argv) {
     std::string scene_path, out_dir, dump_path, dump_full_path, env_map_path;
     bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false, denoise = false;
     int n_gpus = 1;
+    double target_error = -1.0; int min_samples = 8; // --target_error: render until the film's error is below it, -s is then the ceiling
     int spp = 1, max_depth = 15, w = 640, h = 480; // DEFAULT_RESOLUTION common/mod.rs:14
     bool have_out = false;
     for (int i = 1; i < argc; ++i) {
@@ -47,15 +48,18 @@ int main(int argc, char **argv) {
                                                                        // renders through ptrs_render_progressive, which publishes the film after every pass (slower than the one-shot render)
         else if (a == "--aov") aov = true;                             // next to render.png: albedo.png, normal.png, depth.png (the first-hit planes of ptrs_render_aov, resolved)
         else if (a == "--denoise") denoise = true;                     // next to render.png: denoised.png (ptrs_denoise on the film and the first-hit planes, default parameters)
+        else if (a == "--target_error") target_error = std::atof(need("--target_error"));  // render blocks of samples (--min_samples, then doubling, at most -s) until ptrs_film_error's
+        else if (a == "--min_samples") min_samples = std::atoi(need("--min_samples"));     // largest tile error is below E (ptrs_render_converged); prints every check and the count it stopped at
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
         else scene_path = a;
     }
     if (scene_path.empty() || (!have_out && dump_path.empty() && dump_full_path.empty())) {
-        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--headless]\n");
+        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--target_error E [--min_samples N]] [--headless]\n");
         return 2;
     }
+    if (target_error >= 0.0 && (n_gpus > 1 || preview || progress)) { std::fprintf(stderr, "error: --target_error does not combine with --gpus, --preview or --progress\n"); return 2; }
     Camera camera; RenderScene scene; std::string err;
     if (!import_scene(scene_path, w, h, camera, scene, err, default_lights, env_map_path)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     if (!dump_full_path.empty()) { if (!dump_scene_full(dump_full_path, camera, scene)) { std::fprintf(stderr, "error: cannot write %s\n", dump_full_path.c_str()); return 1; } if (!have_out && dump_path.empty()) return 0; }
@@ -78,6 +82,14 @@ int main(int argc, char **argv) {
         for (int d = 0; rc == PTRS_OK && d < n_gpus; ++d) {
             std::fprintf(stderr, "INFO device %d: rows %d..%d, %llu rays\n", d, bands[(size_t)d], bands[(size_t)d + 1], (unsigned long long)(sts[(size_t)d].rays_extension + sts[(size_t)d].rays_shadow + sts[(size_t)d].rays_mis));
             st.samples += sts[(size_t)d].samples; st.rays_extension += sts[(size_t)d].rays_extension; st.rays_shadow += sts[(size_t)d].rays_shadow; st.rays_mis += sts[(size_t)d].rays_mis;
+        }
+    } else if (target_error >= 0.0) {
+        PtrsConvergeResult res{};
+        rc = integrator.render_converged(camera, scene, (float)target_error, (uint32_t)(min_samples < 0 ? 0 : min_samples), res, &st);
+        if (rc == PTRS_OK) {
+            for (uint32_t k = 0; k < res.n_checks; ++k) std::fprintf(stderr, "INFO check %u: %u spp, max tile error %.6g\n", k + 1, res.history[k].spp, (double)res.history[k].max_tile_error);
+            std::fprintf(stderr, "INFO stopped at %u spp (%s, target %.6g, worst tile %u)\n", res.spp_done, res.converged ? "converged" : "ceiling reached", target_error, res.worst_tile);
+            integrator.set_samples_per_pixel((int)res.spp_done); // --aov / --denoise: the planes of the samples the film holds
         }
     } else rc = integrator.render(camera, scene, &st);
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -193,6 +193,14 @@ int PathIntegrator::render(Camera &camera, RenderScene &scene, PtrsStats *stats)
     if (rc != PTRS_OK) last_error = ptrs_last_error();
     return rc;
 }
+int PathIntegrator::render_converged(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsConvergeResult &result, PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    const PtrsRenderParams p = params(camera);
+    rc = ptrs_render_converged(gpu_scene_, &camera.abi, &p, target_error, min_spp, camera.film.pixels.data(), nullptr, &result, stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
 
 bool probe_row_cost(PtrsScene *scene, const PtrsCamera &camera, const PtrsRenderParams &params, int /* strips: the old form's; ignored */, std::vector<float> &row_cost, std::string &err) {
     row_cost.assign((size_t)params.height, 0.0f);

@@ -99,6 +99,12 @@ public:
     // a-trous filter of DESIGN 11 with `dp` (nullptr: ptrs_denoise_default_params).  camera.film keeps the noisy film; out receives
     // width x height pixels, rgb = colour, weight = 1.
     int denoise(Camera &camera, RenderScene &scene, std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES], std::vector<PtrsFilmPixel> &out, const PtrsDenoiseParams *dp = nullptr, PtrsStats *stats = nullptr);
+    // ptrs_render_converged: blocks of samples (min_spp, then doubling; the sampler's spp is the ceiling) into camera.film until
+    // ptrs_film_error's max_tile_error is below target_error.  result: the count it stopped at, whether the last check
+    // was below the target, and (spp, error) of every check.  The film is bit-identical to a render of result.spp_done samples' range.
+    int render_converged(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsConvergeResult &result, PtrsStats *stats = nullptr);
+    // another sample count for the renders that follow (the planes of render_aov at the count render_converged stopped at)
+    void set_samples_per_pixel(int spp) { sb_ = SamplerBuilder(spp, sb_.sample_bounds); }
     // When set, render() publishes the film after every pass of the pipeline (ptrs_render_progressive) and calls this with
     // (passes done, passes in total, first row, one past the last row that changed): the hook a preview gets instead of the
     // reference's second thread that reads the film every 2 s (headless.rs:197-214).

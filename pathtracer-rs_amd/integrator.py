@@ -46,6 +46,15 @@ def load_library():
             raise PtrsError("ABI struct %s: library %d bytes, binding %d bytes" % (s.__name__, L.ptrs_abi_sizeof(i), C.sizeof(s)))
     if L.ptrs_abi_sizeof(11) != C.sizeof(abi.PtrsDenoiseParams):
         raise PtrsError("ABI struct PtrsDenoiseParams: library %d bytes, binding %d bytes" % (L.ptrs_abi_sizeof(11), C.sizeof(abi.PtrsDenoiseParams)))
+    for i, s in ((12, abi.PtrsTileError), (13, abi.PtrsFilmErrorSummary), (14, abi.PtrsConvergeResult)):
+        if L.ptrs_abi_sizeof(i) != C.sizeof(s):
+            raise PtrsError("ABI struct %s: library %d bytes, binding %d bytes" % (s.__name__, L.ptrs_abi_sizeof(i), C.sizeof(s)))
+    L.ptrs_render_range.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_render_range_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_film_error.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_film_error_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_converge_schedule.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.ptrs_render_converged.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptrs_set_option.argtypes = [C.c_char_p, C.c_int64]
     L.ptrs_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.ptrs_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
@@ -262,6 +271,59 @@ class PathIntegrator:
         self.last_stats = stats
         return stats
 
+    def render_range(self, camera, scene, sample_begin, sample_end, half=None, row_begin=0, row_end=0, flags=0, samples=None):
+        """ptrs_render_range: samples [sample_begin, sample_end) of this integrator's render (the sampler's spp stays the whole render's
+        count) accumulated into camera.film.pixels and, when given, into `half` (an (H, W) FILM_DTYPE array).  samples: None, or the
+        (H + 4, W + 4, spp, 3) float32 array of render(want_samples=True), of which only the range's entries are written.  With a pass
+        plan that keeps the band's rows in one pass, successive ranges that tile [0, spp) give render()'s film bit for bit."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end, flags)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        film = camera.film.pixels
+        if half is not None and (half.dtype != abi.FILM_DTYPE or half.shape != film.shape or not half.flags.c_contiguous):
+            raise PtrsError("render_range: half must be a contiguous (H, W) FILM_DTYPE array")
+        if samples is not None:
+            spp = p.spp if p.sampler == abi.SAMPLER_STRATIFIED else round_up_pow2(p.spp)
+            if samples.dtype != np.float32 or samples.shape != (p.height + 4, p.width + 4, spp, 3) or not samples.flags.c_contiguous:
+                raise PtrsError("render_range: samples must be a contiguous (H + 4, W + 4, spp, 3) float32 array")
+        _check(load_library().ptrs_render_range(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), film.ctypes.data,
+                                                half.ctypes.data if half is not None else None, samples.ctypes.data if samples is not None else None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_range_device(self, camera, scene, sample_begin, sample_end, film_device_ptr, half_device_ptr=0, stream=0, row_begin=0, row_end=0, flags=0):
+        """Same, the film (and the half film, 0: none) in device memory (width*height*16 bytes each)."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end, flags)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        _check(load_library().ptrs_render_range_device(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), int(film_device_ptr),
+                                                       int(half_device_ptr) or None, int(stream) or None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_converged(self, camera, scene, target_error, min_spp=8, want_half=False):
+        """ptrs_render_converged: renders blocks of samples (converge_schedule: min_spp, then doubling up to the sampler's spp, the
+        ceiling) into camera.film.pixels until film_error's max_tile_error is below target_error.  The films stay on the device between
+        the blocks.  Returns a dict: spp_done, converged, history = [(spp, max_tile_error) per check], worst_tile, and with want_half
+        the half film the last check was made against.  The film is render_range(0, spp_done)'s; at the ceiling it is render()'s."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        res = abi.PtrsConvergeResult()
+        film = camera.film.pixels
+        half = np.zeros_like(film) if want_half else None
+        _check(load_library().ptrs_render_converged(ds.handle, C.addressof(cam), C.addressof(p), float(target_error), int(min_spp), film.ctypes.data,
+                                                    half.ctypes.data if want_half else None, C.addressof(res), C.addressof(stats)))
+        self.last_stats = stats
+        out = dict(spp_done=int(res.spp_done), converged=bool(res.converged), worst_tile=int(res.worst_tile),
+                   history=[(int(res.history[k].spp), float(res.history[k].max_tile_error)) for k in range(res.n_checks)])
+        if want_half:
+            out["half"] = half
+        return out
+
     def render_denoised(self, camera, scene, **params):
         """render, then render_aov, then Denoiser.denoise (params: iterations, sigma_color, sigma_normal, sigma_depth, demodulate).  The
         noisy film stays in camera.film; returns the denoised (H, W) FILM_DTYPE pixels (rgb = colour, weight = 1)."""
@@ -392,6 +454,35 @@ class Denoiser:
             self.close()
         except Exception:
             pass
+
+
+def film_error(film, half, device=0, want_tiles=True):
+    """ptrs_film_error: two (H, W) FILM_DTYPE films in host memory, `half` holding half of `film`'s samples -> (tiles, summary): the
+    (tiles_y, tiles_x) TILE_DTYPE records of the 16 x 16 tiles (None without want_tiles) and the PtrsFilmErrorSummary."""
+    if film.dtype != abi.FILM_DTYPE or half.dtype != abi.FILM_DTYPE or film.ndim != 2 or half.shape != film.shape or not film.flags.c_contiguous or not half.flags.c_contiguous:
+        raise PtrsError("film_error: film and half must be contiguous (H, W) FILM_DTYPE arrays of one shape")
+    H, W = film.shape
+    tiles = np.zeros(((H + abi.PtrsErrorTile - 1) // abi.PtrsErrorTile, (W + abi.PtrsErrorTile - 1) // abi.PtrsErrorTile), dtype=abi.TILE_DTYPE) if want_tiles else None
+    s = abi.PtrsFilmErrorSummary()
+    _check(load_library().ptrs_film_error(int(device), W, H, film.ctypes.data, half.ctypes.data, tiles.ctypes.data if want_tiles else None, C.addressof(s)))
+    return tiles, s
+
+
+def film_error_device(width, height, film_device_ptr, half_device_ptr, tiles_device_ptr, device=0, stream=0):
+    """ptrs_film_error_device: the films and the tile records (tiles_x * tiles_y * 8 bytes) in device memory -> the summary."""
+    s = abi.PtrsFilmErrorSummary()
+    _check(load_library().ptrs_film_error_device(int(device), int(width), int(height), int(film_device_ptr) or None, int(half_device_ptr) or None,
+                                                 int(tiles_device_ptr) or None, int(stream) or None, C.addressof(s)))
+    return s
+
+
+def converge_schedule(spp, min_spp):
+    """ptrs_converge_schedule (a pure function, no device): the blocks of render_converged as (begin, middle, end) -- [begin, middle)
+    goes to the film and the half film, [middle, end) to the film only; an error check follows every block."""
+    b = np.zeros((abi.PtrsConvergeMaxChecks, 3), dtype=np.uint32)
+    n = C.c_uint32(0)
+    _check(load_library().ptrs_converge_schedule(int(spp), int(min_spp), b.ctypes.data, C.addressof(n)))
+    return [tuple(int(v) for v in r) for r in b[: n.value]]
 
 
 def _aov_mask(planes):
