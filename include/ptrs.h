@@ -213,7 +213,7 @@ typedef struct PtrsStats {
     uint64_t debug[12];      /* zero in product builds; diagnostic builds (-DPTRS_STAMPS): wave-clock sums per phase of k_shade; ptrs_denoise with PTRS_DENOISE_TIMING: nanoseconds per launch */
     /* how the queue kernels of the call's last pass were launched (ABI 3): segments per queue (one wave each), and per kernel class
      * [0] extend, [1] connect, [2] shade, [3] aux the workgroups of the last launch and the resident workgroups per CU the launch was
-     * sized for (hipOccupancyMaxActiveBlocksPerMultiprocessor) */
+     * sized for (hipOccupancyMaxActiveBlocksPerMultiprocessor, capped by what the CU's LDS holds in allocation granules) */
     uint64_t queue_segments;
     uint64_t grid_wgs[4];
     uint64_t resident_wgs_per_cu[4];
@@ -225,6 +225,10 @@ typedef struct PtrsStats {
     double ms_tail;          /* its kernels (PTRS_FLAG_TIMING; their traversal and shading are not in ms_trace / ms_shade) */
     uint64_t tail_launches;
     uint64_t tail_round;     /* the round at which the call's last pass handed over, 0xffffffff: it did not */
+    /* the traversal form the scene's kernels were chosen for: LDS stack entries per lane (8, 9 or 16), and the 16-byte vectors the
+     * scene's pair tree and triangles take in LDS form (0: quad form, traversed out of memory) */
+    uint64_t stack_lds;
+    uint64_t lds_form_v4;
 } PtrsStats;
 
 enum {

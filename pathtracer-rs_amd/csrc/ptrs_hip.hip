@@ -509,20 +509,39 @@ __device__ inline void resolve_wave(const DScene &sc, const DPaths &P, const DQu
 // and take 4-14 spilled ones at 96, almost all in the epilogue / resolve code behind the loop: classroom extend 211 -> 197 ms, connect
 // 340 -> 319 ms, frame 923 -> 863 ms.  A sixth wave (80 registers, and only 21 instead of 85 top records in LDS to make room) loses it
 // again: colonnade +3 %, classroom +1 %.  LDS form: 6 (the loop needs 61-76 registers); a 10-entry stack column that spares Cornell's tree
-// (9 entries) the spill code costs the sixth workgroup per CU and 3 % of the extension kernel.
+// (9 entries) the spill code costs the sixth workgroup per CU and 3 % of the extension kernel (20 480 + 10 240 B: 24 granules, five fit).
 #ifndef PTRS_QUAD_WAVES
 #define PTRS_QUAD_WAVES 5
 #endif
 #ifndef PTRS_LDS_WAVES
 #define PTRS_LDS_WAVES 6
 #endif
-template <int FEAT, int DEPTH, int GEOM> struct TravWaves { enum { N = (GEOM == 640 || GEOM == 544) ? PTRS_LDS_WAVES : ((GEOM == 0 && DEPTH == 8) ? PTRS_QUAD_WAVES : 0) }; };
-// (GEOM = 544 with a 9-entry column: a small scene whose pair tree is one level deeper than the 8-entry column -- Cornell: 527 vectors of LDS form, depth 9 --
-// gets the column it needs and a staging area cut to fit: 18 432 + 8 704 B, six workgroups per CU like the 8 / 640 form, and kernels WITHOUT overflow code, whose
-// node visit pushes in select form (lf_node_visit).  Alone the 9 / 544 form measured within noise of 8 / 640 + overflow; with the select-form push the
-// four-lane Cornell frame went 142.96 -> 139.22 ms (ABAB x 3), the single-lane kernels unchanged: fewer scalar instructions to share the SIMDs' scalar port among
-// the lanes' kernels.)
+// LDS accounting, one for the kernels' sizes, the launch sizing and the reported residency.  A CU has 160 KB of LDS and hands it out in
+// granules of 1 280 B (320 dwords; measured, tools/lds_residency.hip -> profiles/lds_residency.json: six workgroups of 26 880 B are
+// resident on a CU, of 26 881 B five), so what a workgroup costs is its static + dynamic LDS rounded UP to the granule, and what fits is
+// counted in those.  hipOccupancyMaxActiveBlocksPerMultiprocessor and the compiler's occupancy remark divide by bytes.
+#ifndef PTRS_LDS_GRANULE
+#define PTRS_LDS_GRANULE 1280
+#endif
+#define PTRS_LDS_PER_CU 163840
+constexpr uint32_t lds_alloc(uint32_t bytes) { return (bytes + (uint32_t)PTRS_LDS_GRANULE - 1u) / (uint32_t)PTRS_LDS_GRANULE * (uint32_t)PTRS_LDS_GRANULE; }
+constexpr uint32_t lds_wgs_per_cu(uint32_t bytes) { return (uint32_t)PTRS_LDS_PER_CU / lds_alloc(bytes ? bytes : 1u); } // workgroups of `bytes` of LDS one CU holds
+constexpr uint32_t lds_stack_bytes(int depth) { return (uint32_t)depth * BLOCK * 8u; } // the traversal-stack column: 8 bytes per entry and thread
+// The staging area of the 9-entry-column LDS form, in 16-byte vectors: the largest for which PTRS_LDS_WAVES workgroups fit a CU beside the column (528).
+constexpr int LDS9_V4 = (int)(((uint32_t)PTRS_LDS_PER_CU / PTRS_LDS_WAVES / PTRS_LDS_GRANULE * PTRS_LDS_GRANULE - lds_stack_bytes(9)) / 16u);
+template <int FEAT, int DEPTH, int GEOM> struct TravWaves { enum { N = (GEOM == 640 || (GEOM == LDS9_V4 && DEPTH == 9)) ? PTRS_LDS_WAVES : ((GEOM == 0 && DEPTH == 8) ? PTRS_QUAD_WAVES : 0) }; };
+// (GEOM = LDS9_V4 with a 9-entry column: a small scene whose pair tree is one level deeper than the 8-entry column -- Cornell: 527 vectors of LDS form, depth 9 --
+// gets the column it needs and a staging area cut to fit: 18 432 + 8 448 B = 26 880 B, 21 granules, six workgroups per CU like the 8 / 640 form (26 624 B, 21
+// granules as well), and kernels WITHOUT overflow code, whose node visit pushes in select form (lf_node_visit).  The form first had 544 vectors, 27 136 B: 22
+// granules, of which only five fit -- it measured "within noise of 8 / 640 + overflow" by itself because it had lost the sixth workgroup to the granule while
+// it shed the overflow code.  With the select-form push the four-lane Cornell frame went 142.96 -> 139.22 ms (ABAB x 3): fewer scalar instructions to share
+// the SIMDs' scalar port among the lanes' kernels.)
 template <int DEPTH, int GEOM> struct TravLds { enum { TOP = GEOM == 0 && DEPTH == 8, V4 = GEOM > 0 ? GEOM : (TOP ? TOP_LDS_STRIDE * QUAD_TOP_NODES : 1) }; }; // quad form with the small stack column: the tree's top lives in LDS
+// what the kernels are compiled for must fit: the waves per SIMD they name (one workgroup = one wave per SIMD), in granules
+template <int DEPTH, int GEOM> constexpr uint32_t trav_lds_bytes() { return lds_stack_bytes(DEPTH) + (uint32_t)TravLds<DEPTH, GEOM>::V4 * 16u; }
+static_assert(LDS9_V4 > 0 && (uint32_t)PTRS_LDS_WAVES * lds_alloc(trav_lds_bytes<9, LDS9_V4>()) <= (uint32_t)PTRS_LDS_PER_CU, "the 9-entry LDS form: PTRS_LDS_WAVES workgroups per CU");
+static_assert((uint32_t)PTRS_LDS_WAVES * lds_alloc(trav_lds_bytes<8, 640>()) <= (uint32_t)PTRS_LDS_PER_CU, "the 8 / 640 LDS form: PTRS_LDS_WAVES workgroups per CU");
+static_assert((uint32_t)PTRS_QUAD_WAVES * lds_alloc(trav_lds_bytes<8, 0>()) <= (uint32_t)PTRS_LDS_PER_CU, "the quad form with the tree's top in LDS: PTRS_QUAD_WAVES workgroups per CU");
 
 // Diagnostic builds only (-DPTRS_STAMPS_EXT, tools/ablate.sh + tools/stamps_ext.py): wave clocks of the phases of the extension stage, summed
 // into Q.stats[CNT_STAMP0 + k] -- 0 retire + bookkeeping, 1 refill (ray loads until the rays are set up), 2 traversal steps, 3 epilogue,
@@ -977,6 +996,7 @@ __global__ __launch_bounds__(BLOCK, (ShadeWaves<MAT, FEAT>::N)) void k_shade(DPa
     __shared__ v4 lds_tri[SH_TRI_V4];
     __shared__ v4 lds_light[SH_LIGHTS * SH_LIGHT_V4];
     __shared__ float lds_marg[ShadeLdsSizes<FEAT, ENVPRE>::MARG ? SH_MARG_WORDS : 1];
+    static_assert(2u * lds_alloc((uint32_t)(sizeof(lds_pf) + sizeof(lds_sob) + sizeof(lds_tri) + sizeof(lds_light) + sizeof(lds_marg))) <= (uint32_t)PTRS_LDS_PER_CU, "two shade workgroups per CU");
     bool err_dim = false;
     if (round_is_dead(Q, it)) return;
     const ShadeCtxLds<ENVPRE> X = stage_shade_tables<FEAT, ENVPRE>(S, sc, cfg, lds_sob, lds_tri, lds_light, lds_marg);
@@ -1019,6 +1039,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tail(DParams R, DSampler S, DCamer
     __shared__ v4 lds_tri[SH_TRI_V4];
     __shared__ v4 lds_light[SH_LIGHTS * SH_LIGHT_V4];
     __shared__ float lds_marg[ShadeLdsSizes<FEAT, false>::MARG ? SH_MARG_WORDS : 1];
+    static_assert(2u * lds_alloc((uint32_t)(sizeof(lds_stack) + sizeof(lds_geom) + sizeof(lds_pf) + sizeof(lds_sob) + sizeof(lds_tri) + sizeof(lds_light) + sizeof(lds_marg))) <= (uint32_t)PTRS_LDS_PER_CU, "two tail workgroups per CU");
     if (round_is_dead(Q, it0)) return;
     LdsGeom LG; LG.root = LG.tri0 = LG.tri_copy = 0;
     const GeomTop GG = stage_top(sc, lds_geom, TravLds<DEPTH, GEOM>::TOP);
@@ -1753,6 +1774,9 @@ struct HipBackend {
         if (itr != ps->occupancy.end()) return opt.persist ? itr->second : 8;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
+        // the API counts LDS by the byte; a CU hands it out in granules (lds_alloc): cap by what fits in those (the queue kernels take no dynamic LDS)
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, key) == hipSuccess) { if (fa.sharedSizeBytes > 0) nb = std::max(1, std::min(nb, (int)lds_wgs_per_cu((uint32_t)fa.sharedSizeBytes))); } else (void)hipGetLastError();
         ps->occupancy[key] = nb > 8 ? 8 : nb;
         return opt.persist ? ps->occupancy[key] : 8;
     }
@@ -1858,7 +1882,7 @@ struct HipBackend {
     // the instantiation of a traversal kernel for this scene: LDS stack depth, spill columns, geometry source, phase voting
     typedef void (*TravFn)(DParams, DScene, StackSpill, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *);
 #define PTRS_PICK(K, D, O, GE) (v ? (TravFn)K<FEAT, D, O, GE, true> : (TravFn)K<FEAT, D, O, GE, false>)
-#define PTRS_PICK_ALL(K) (ps->stack_lds == 9 ? PTRS_PICK(K, 9, false, 544) : ps->stack_lds == 8 ? (geom4 <= 640 ? (ovf ? PTRS_PICK(K, 8, true, 640) : PTRS_PICK(K, 8, false, 640)) : geom4 <= 1536 ? (ovf ? PTRS_PICK(K, 8, true, 1536) : PTRS_PICK(K, 8, false, 1536)) : (ovf ? PTRS_PICK(K, 8, true, 0) : PTRS_PICK(K, 8, false, 0))) \
+#define PTRS_PICK_ALL(K) (ps->stack_lds == 9 ? PTRS_PICK(K, 9, false, LDS9_V4) : ps->stack_lds == 8 ? (geom4 <= 640 ? (ovf ? PTRS_PICK(K, 8, true, 640) : PTRS_PICK(K, 8, false, 640)) : geom4 <= 1536 ? (ovf ? PTRS_PICK(K, 8, true, 1536) : PTRS_PICK(K, 8, false, 1536)) : (ovf ? PTRS_PICK(K, 8, true, 0) : PTRS_PICK(K, 8, false, 0))) \
                                               : (ovf ? PTRS_PICK(K, 16, true, 0) : PTRS_PICK(K, 16, false, 0)))
     template <int FEAT> TravFn pick_extend(bool v, bool ovf) { return PTRS_PICK_ALL(k_extend_rf); }
     template <int FEAT> TravFn pick_connect(bool v, bool ovf) { return PTRS_PICK_ALL(k_connect_rf); }
@@ -1948,7 +1972,7 @@ struct HipBackend {
         int kind = -1;
         for (int k = 0; k < 7; ++k) if (ps->H.kinds_present[k]) { if (kind >= 0) return nullptr; kind = k; }
         const bool ovf = ps->spill.p != nullptr;
-        if (ps->stack_lds == 9) return (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE) ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 544, false, 9> : nullptr;
+        if (ps->stack_lds == 9) return (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE) ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, LDS9_V4, false, 9> : nullptr;
         if (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE) {
             if (geom4 <= 640) return ovf ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 640, true> : (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 640, false>;
             if (geom4 <= 1536) return ovf ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 1536, true> : (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 1536, false>;
@@ -2090,6 +2114,7 @@ struct HipBackend {
         }
         st.ms_trace = st.ms_extend + st.ms_connect; st.ms_shade = st.ms_shade_kernels + st.ms_aux;
         st.queue_segments = G; st.lanes = n_lanes; st.grid_pct = (uint64_t)(opt.grid_pct ? opt.grid_pct : 100);
+        st.stack_lds = ps->stack_lds; st.lds_form_v4 = geom4 == 0xffffffffu ? 0u : geom4;
         { const int cls[4] = {T_EXTEND, T_CONNECT, T_SHADE, T_AUX}; for (int k = 0; k < 4; ++k) { st.grid_wgs[k] = last_grid[cls[k]]; st.resident_wgs_per_cu[k] = last_per_cu[cls[k]]; } }
         st.extend_launches = cat_launches[T_EXTEND]; st.connect_launches = cat_launches[T_CONNECT]; st.shade_launches = cat_launches[T_SHADE]; st.aux_launches = cat_launches[T_AUX]; st.film_launches = cat_launches[T_FILM]; st.tail_launches = cat_launches[T_TAIL]; st.tail_round = tail_at_last;
         size_t bytes = 0;
@@ -2332,7 +2357,7 @@ static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScen
     // against a 16-entry column without the cache: +2 % on colonnade, +1 % on classroom).  the option stack_lds = 16 selects that
     // older layout for quad-form scenes.
     ps->stack_lds = (H.use_quad && opt.stack_lds == 16) ? 16u : 8u;
-    if (!H.use_quad && opt.stack_lds != 16 && H.stack_bound == 9u && LN_V4 * (uint32_t)H.nodes2.size() + 9u * (uint32_t)H.tris.size() <= 544u) ps->stack_lds = 9u; // the 9 / 544 LDS form (TravWaves): no overflow code
+    if (!H.use_quad && opt.stack_lds != 16 && H.stack_bound == 9u && LN_V4 * (uint32_t)H.nodes2.size() + 9u * (uint32_t)H.tris.size() <= (uint32_t)LDS9_V4) ps->stack_lds = 9u; // the 9-entry LDS form (TravWaves, LDS9_V4 = 528 vectors): no overflow code; a larger scene of that depth takes 8 / 640 + overflow
     if (H.stack_bound > ps->stack_lds) {
         const size_t threads = (size_t)ps->n_cu * 8 * BLOCK; // no launch holds more than 8 workgroups per CU
         ps->spill_lane_elems = threads * (size_t)(H.stack_bound - ps->stack_lds);
@@ -2963,6 +2988,7 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         }
         stats->ms_trace = ms; stats->ms_extend = ms; stats->trace_launches = repeats; stats->extend_launches = repeats; stats->kernel_launches = repeats + 1; stats->rays_extension = (uint64_t)n * repeats;
         stats->queue_segments = G; stats->grid_wgs[0] = grid; stats->resident_wgs_per_cu[0] = be.last_per_cu[HipBackend::T_EXTEND];
+        stats->stack_lds = scene->stack_lds; stats->lds_form_v4 = be.geom4 == 0xffffffffu ? 0u : be.geom4;
         cleanup();
         if (e != hipSuccess) { g_err = std::string("ptrs_trace_bench: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
         return PTRS_OK;
