@@ -4,7 +4,7 @@
 // and weights of the beauty image.  Everything that is needed sits in the pipeline after round 0 -- the hit (triangle id, barycentrics)
 // in P.hit, the film position in P.pfilm -- so an AOV call is a render cut after its first extension: generate, extend(0), then
 //   aov_item          : camera_ray -> tri_surface -> surface_differentials -> the NormalMaterial chain (make_bsdf's order) -> the values
-//   render_aov_impl   : render_impl's sample grid, sampler, row bands, pass plan and lanes around those three stages and the plane films
+//   render_aov_impl   : render_impl's set-up, pass plan and lanes around those three stages and the plane films
 // Specular first hits are not followed: a mirror shows the mirror's own surface.  The reference has no such call.
 #pragma once
 #include "pt_render.h"
@@ -71,8 +71,8 @@ PT_HD void aov_sample_row(const AovRec &a, float *o) {
     o[8] = a.p.x; o[9] = a.p.y; o[10] = a.p.z; o[11] = u2f(a.prim);
 }
 
-// The AOV call: render_impl's argument checks, sample grid, sampler set-up, row bands, pass plan and lanes (the same plan: a plane's
-// weight channel is then formed by the very additions of the beauty film's) with max_depth forced to 0, and per pass
+// The AOV call: render_impl's set-up and pass plan (render_setup, plan_passes: a plane's weight channel is then formed by the very
+// additions of the beauty film's) with max_depth forced to 0, and per pass
 //     pass_begin -> generate -> extend(0) -> aov -> the plane films, chained in pass order.
 // The survival profile of the scene (be.learn / be.tail_round) belongs to beauty renders and is neither read nor fed.
 // A plan that cuts the band's ROWS into blocks (a band of one sample exceeds the pass capacity: then every pass holds one sample index)
@@ -86,72 +86,27 @@ int render_aov_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uin
                     uint32_t planes, const DAovFilm &films /* backend memory, W*H each */, float *samples_out /* backend memory or null */, PtrsStats *stats, std::string &err) {
     using clock = std::chrono::steady_clock;
     auto t_begin = clock::now();
-    if (prm_in.width <= 0 || prm_in.height <= 0 || prm_in.spp <= 0 || prm_in.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
-    if (bvh_depth > 64) { err = "BVH deeper than the 64-entry traversal stack (accelerator.rs:370)"; return PTRS_ERR_UNSUPPORTED; }
+    if (prm_in.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
     PtrsRenderParams prm = prm_in;
     prm.max_depth = 0; // the pass ends behind its first extension: the epilogue buckets nothing
-    SampleGrid g = make_sample_grid(prm.width, prm.height, prm.spp);
-    uint32_t strat_dim = 0;
-    if (prm.sampler == PTRS_SAMPLER_STRATIFIED) {
-        strat_dim = 1; while ((strat_dim + 1u) * (strat_dim + 1u) <= (uint32_t)prm.spp) ++strat_dim;
-        if (strat_dim * strat_dim != (uint32_t)prm.spp) { err = "stratified sampler: spp must be dim_pixel_samples squared"; return PTRS_ERR_INVALID; }
-        if (prm.n_sampled_dimensions < 3 * (prm.max_depth + 1) + 1 || prm.n_sampled_dimensions > 63) { err = "stratified sampler: n_sampled_dimensions must be 4 .. 63"; return PTRS_ERR_UNSUPPORTED; }
-        g.spp = strat_dim * strat_dim;
-    } else if (prm.sampler != PTRS_SAMPLER_SOBOL) { err = "unknown sampler"; return PTRS_ERR_INVALID; }
-    if (g.log2_res < 1 || g.log2_res > 25 || 2u * g.log2_res + (31u - (uint32_t)__builtin_clz(g.spp)) > 62u) { err = "resolution / spp outside the Sobol index range"; return PTRS_ERR_UNSUPPORTED; }
-    int32_t rb = prm.row_begin, re = prm.row_end;
-    if (re <= rb) { rb = 0; re = prm.height; }
-    if (rb < 0 || re > prm.height) { err = "row band outside the film"; return PTRS_ERR_INVALID; }
-    const int32_t srow0 = std::max(rb, 0), srow1 = std::min(re + 4, g.NY); // sample rows (grid coordinates) whose footprint can touch output rows [rb, re)
+    RenderSetup u;
+    int rc = render_setup(be, bvh_depth, cam, prm, RenderJob{}, u, err);
+    if (rc != PTRS_OK) return rc;
+    const SampleGrid &g = u.g;
+    const int32_t rb = u.rb, re = u.re, srow0 = u.srow0, srow1 = u.srow1;
+    DParams R = u.R;
 
-    DSampler S;
-    S.matrices = be.sobol_matrices(); S.bytetab = be.sobol_bytetab(); S.nibtab = be.sobol_nibtab(); S.vdc = be.sobol_vdc(g.log2_res - 1); S.vdc_inv = be.sobol_vdc_inv(g.log2_res - 1);
-    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
-    S.kind = (uint32_t)prm.sampler; S.strat_dims = (uint32_t)prm.n_sampled_dimensions; S.strat1 = nullptr; S.strat2 = nullptr;
-    if (strat_dim) {
-        int rc_t = be.strat_tables(g.NX, g.NY, strat_dim, S.strat_dims, &S.strat1, &S.strat2, err);
-        if (rc_t != PTRS_OK) return rc_t;
-    }
-    DCamera C;
-    std::memcpy(C.rot, cam.rot, 16); std::memcpy(C.trans, cam.trans, 12);
-    C.m00 = cam.m00; C.m11 = cam.m11; C.m22 = cam.m22; C.m23 = cam.m23;
-    std::memcpy(C.r2s, cam.raster_to_screen, 64); std::memcpy(C.dxc, cam.dx_camera, 12); std::memcpy(C.dyc, cam.dy_camera, 12);
-    DParams R;
-    std::memset(&R, 0, sizeof(R));
-    R.max_depth = 0; R.rr_threshold = prm.rr_threshold; R.rr_start_depth = prm.rr_start_depth; R.rr_enable = prm.rr_enable;
-    R.NX = g.NX; R.NY = g.NY; R.W = prm.width; R.H = prm.height;
-    R.inv_sqrt_spp = 1.0f / std::sqrt((float)g.spp);
-    R.counters_on = (prm.flags & PTRS_FLAG_COUNTERS) ? 1u : 0u;
-
-    // ---- pass planning: render_impl's, line for line ------------------------------------------
-    const uint32_t n_lanes = std::max(1u, be.lanes((uint64_t)(srow1 - srow0) * (uint64_t)g.NX * (uint64_t)g.spp, sc_host_feat.kinds_present, false, g.spp));
+    const uint64_t band_rows = (uint64_t)(srow1 - srow0);
+    const uint32_t n_lanes = std::max(1u, be.lanes(band_rows * (uint64_t)g.NX * (uint64_t)g.spp, sc_host_feat.kinds_present, false, g.spp));
     uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, sc_host_feat.kinds_present));
     if (capacity < (uint64_t)g.NX) capacity = (uint64_t)g.NX;
-    const uint64_t band_rows = (uint64_t)(srow1 - srow0);
-    uint64_t rows_per_pass, samples_per_pass;
-    if (band_rows * (uint64_t)g.NX <= capacity) {
-        rows_per_pass = band_rows;
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
-        const uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
-        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
-    } else {
-        samples_per_pass = 1;
-        const uint64_t rows_max = std::max<uint64_t>(1, capacity / (uint64_t)g.NX);
-        const uint64_t n_chunks = (band_rows + rows_max - 1) / rows_max;
-        rows_per_pass = (band_rows + n_chunks - 1) / n_chunks;
-    }
-    if (n_lanes > 1 && band_rows * (uint64_t)g.NX <= capacity && !prm.paths_per_pass) {
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(g.spp, capacity / (band_rows * (uint64_t)g.NX)));
-        uint64_t n_chunks = (g.spp + spp_max - 1) / spp_max;
-        if (g.spp >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes;
-        samples_per_pass = (g.spp + n_chunks - 1) / n_chunks;
-    }
-    const uint64_t max_paths = rows_per_pass * (uint64_t)g.NX * samples_per_pass;
-    if (max_paths >= 0xffffffffull) { err = "pass too large"; return PTRS_ERR_INVALID; }
+    PassPlan pp;
+    if (!plan_passes(band_rows, (uint64_t)g.NX, g.spp, capacity, n_lanes, prm.paths_per_pass != 0, pp)) { err = "pass too large"; return PTRS_ERR_INVALID; }
+    const uint64_t rows_per_pass = pp.rows_per_pass, samples_per_pass = pp.samples_per_pass;
 
     const uint32_t count_rows = 2u; // round 0, and the row its kernels may look ahead to
     const int feat = scene_features(sc_host_feat), feat_trace = scene_trace_features(sc_host_feat);
-    int rc = be.begin(sc, S, C, (uint32_t)max_paths, count_rows, bvh_depth, prm.flags, feat, feat_trace, err);
+    rc = be.begin(sc, u.S, u.C, (uint32_t)pp.max_paths, count_rows, bvh_depth, prm.flags, feat, feat_trace, err);
     if (rc != PTRS_OK) return rc;
 
     PtrsStats st;

@@ -515,4 +515,14 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
     return PTRS_OK;
 }
 
+// The scene as the stage functions read it, over the host copy's own arrays (the test twins; H must outlive the view)
+inline DScene host_scene_view(const HostScene &H) {
+    DScene sc;
+    sc.nodes2 = H.nodes2.data(); sc.n_nodes2 = (uint32_t)H.nodes2.size(); sc.nodes4 = H.nodes4.data(); sc.n_nodes4 = (uint32_t)H.nodes4.size();
+    sc.nodes = H.nodes.data(); sc.tris = H.tris.data(); sc.shade = H.shade.data(); sc.mats = H.mats.data(); sc.texs = H.texs.data();
+    sc.levels = H.levels.data(); sc.texdata = H.texdata.data(); sc.lights = H.lights.data(); sc.distdata = H.distdata.data(); sc.inf_lights = H.inf_lights.data();
+    sc.n_nodes = (uint32_t)H.nodes.size(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
+    return sc;
+}
+
 } // namespace pt

@@ -152,109 +152,152 @@ struct RenderProgress { void (*fn)(void *user, uint32_t done, uint32_t total, in
 // (round 0: the camera rays; round k: the rays leaving the paths' k-th vertices) -- ray sets of a real frame for the traversal bench.
 struct RayDump { uint32_t round, max_rays; float *out /* backend memory, max_rays x 7: o, d, t_max */; uint32_t *n_out /* host */; };
 
+// What a render call is asked for beyond camera and parameters.  Pointers are back-end memory unless noted; null / default: not asked for.
+struct RenderJob {
+    v4 *film = nullptr;                      // W*H
+    v4 *film_half = nullptr;                 // W*H: a second film that receives the same samples (a second gather of every pass, chained in the same order)
+    float *samples_out = nullptr;
+    PtrsStats *stats = nullptr;              // host
+    const RenderProgress *progress = nullptr; // called after every pass with the rows it touched (back end copies them out first)
+    const RayDump *dump = nullptr;
+    const int32_t *single_pixel = nullptr;   // render_single_pixel (integrator.rs:505-534): raster (px, py), any pixel of the sample bounds; traces that pixel's spp paths only, no film, samples_out = spp * 3 floats
+    uint32_t *row_cost = nullptr;            // NY counters (zeroed by the caller): the BVH queries of every sample row's paths are added; no film
+    const uint32_t *sample_range = nullptr;  // host.  ptrs_render_range: {begin, end}, samples [begin, end) of the spp-sample render (null: all of them).  The passes run over the range; the sampler, the sample layout and the ray differentials stay those of the whole render
+};
+
+inline DCamera make_camera(const PtrsCamera &cam) {
+    DCamera C;
+    std::memcpy(C.rot, cam.rot, 16); std::memcpy(C.trans, cam.trans, 12);
+    C.m00 = cam.m00; C.m11 = cam.m11; C.m22 = cam.m22; C.m23 = cam.m23;
+    std::memcpy(C.r2s, cam.raster_to_screen, 64); std::memcpy(C.dxc, cam.dx_camera, 12); std::memcpy(C.dyc, cam.dy_camera, 12);
+    return C;
+}
+
+// The Sobol' sampler of a sample grid over a back end's five tables (vdc / vdc_inv: row log2_res - 1); render_setup adds what a stratified render needs
+inline DSampler make_sampler(const SampleGrid &g, const uint32_t *matrices, const uint32_t *bytetab, const uint32_t *nibtab, const uint64_t *vdc, const uint64_t *vdc_inv) {
+    DSampler S;
+    S.matrices = matrices; S.bytetab = bytetab; S.nibtab = nibtab; S.vdc = vdc; S.vdc_inv = vdc_inv;
+    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
+    S.kind = PTRS_SAMPLER_SOBOL; S.strat_dims = 0; S.strat1 = nullptr; S.strat2 = nullptr;
+    return S;
+}
+
+// Everything a render has settled before its passes are planned: render_impl's and render_aov_impl's common head.
+struct RenderSetup {
+    SampleGrid g;
+    uint32_t strat_dim;       // stratified sampler: dim_pixel_samples, else 0
+    uint32_t sb, se;          // the samples this call traces
+    int32_t rb, re;           // output rows
+    int32_t srow0, srow1;     // sample rows (grid coordinates) whose footprint can touch output rows [rb, re)
+    DSampler S; DCamera C;
+    DParams R;                // the part that is the same for every pass
+};
 template <class BE>
-int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm,
-                v4 *film /* backend memory, W*H */, float *samples_out /* backend memory or null */, PtrsStats *stats, std::string &err,
-                const RenderProgress *progress = nullptr /* called after every pass with the rows it touched (back end copies them out first) */,
-                const RayDump *dump = nullptr,
-                const int32_t *single_pixel = nullptr /* render_single_pixel (integrator.rs:505-534): raster (px, py), any pixel of the sample bounds;
-                                                         traces that pixel's spp paths only, no film, samples_out = spp * 3 floats */,
-                uint32_t *row_cost = nullptr /* backend memory, NY counters (zeroed by the caller): the BVH queries of every sample row's paths are added; no film */,
-                const uint32_t *sample_range = nullptr /* ptrs_render_range: {begin, end}, samples [begin, end) of the spp-sample render (null: all of them).  The passes run
-                                                          over the range; the sampler, the sample layout and the ray differentials stay those of the whole render */,
-                v4 *film_half = nullptr /* backend memory, W*H: a second film that receives the same samples (a second gather of every pass, chained in the same order) */) {
-    using clock = std::chrono::steady_clock;
-    const bool *kinds_present = sc_host_feat.kinds_present;
-    auto t_begin = clock::now();
+int render_setup(BE &be, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm, const RenderJob &job, RenderSetup &u, std::string &err) {
     if (prm.width <= 0 || prm.height <= 0 || prm.spp <= 0 || prm.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
     if (bvh_depth > 64) { err = "BVH deeper than the 64-entry traversal stack (accelerator.rs:370)"; return PTRS_ERR_UNSUPPORTED; }
-    SampleGrid g = make_sample_grid(prm.width, prm.height, prm.spp);
-    uint32_t strat_dim = 0;
+    u = RenderSetup{};
+    SampleGrid &g = u.g;
+    g = make_sample_grid(prm.width, prm.height, prm.spp);
     if (prm.sampler == PTRS_SAMPLER_STRATIFIED) { // StratifiedSamplerBuilder::new(log, dim_pixel_samples, n_sampled_dimensions) (stratified.rs:22-36)
+        uint32_t &strat_dim = u.strat_dim;
         strat_dim = 1; while ((strat_dim + 1u) * (strat_dim + 1u) <= (uint32_t)prm.spp) ++strat_dim;
         if (strat_dim * strat_dim != (uint32_t)prm.spp) { err = "stratified sampler: spp must be dim_pixel_samples squared"; return PTRS_ERR_INVALID; }
         if (prm.n_sampled_dimensions < 3 * (prm.max_depth + 1) + 1 || prm.n_sampled_dimensions > 63) {
             err = "stratified sampler: n_sampled_dimensions must cover the path (3 * (max_depth + 1) + 1 .. 63): draws past it come from the tile's generator in path order (sampler/mod.rs:137-151), which a wavefront cannot reproduce";
             return PTRS_ERR_UNSUPPORTED;
         }
-        if (single_pixel) { err = "render_single_pixel with the stratified sampler is not supported (its tables depend on the tile's earlier pixels)"; return PTRS_ERR_UNSUPPORTED; }
+        if (job.single_pixel) { err = "render_single_pixel with the stratified sampler is not supported (its tables depend on the tile's earlier pixels)"; return PTRS_ERR_UNSUPPORTED; }
         g.spp = strat_dim * strat_dim;
     } else if (prm.sampler != PTRS_SAMPLER_SOBOL) { err = "unknown sampler"; return PTRS_ERR_INVALID; }
-    const uint32_t sb = sample_range ? sample_range[0] : 0u, se = sample_range ? sample_range[1] : g.spp; // the samples this call traces
-    if (!(sb < se && se <= g.spp)) { err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(g.spp) + " for these parameters)"; return PTRS_ERR_INVALID; }
-    if (film_half && film_half == film) { err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
-    const uint32_t ns = se - sb;
+    u.sb = job.sample_range ? job.sample_range[0] : 0u; u.se = job.sample_range ? job.sample_range[1] : g.spp;
+    if (!(u.sb < u.se && u.se <= g.spp)) { err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(g.spp) + " for these parameters)"; return PTRS_ERR_INVALID; }
+    if (job.film_half && job.film_half == job.film) { err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
     if (g.log2_res < 1 || g.log2_res > 25 || 2u * g.log2_res + (31u - (uint32_t)__builtin_clz(g.spp)) > 62u) { err = "resolution / spp outside the Sobol index range"; return PTRS_ERR_UNSUPPORTED; }
-    int32_t rb = prm.row_begin, re = prm.row_end;
-    if (re <= rb) { rb = 0; re = prm.height; }
-    if (rb < 0 || re > prm.height) { err = "row band outside the film"; return PTRS_ERR_INVALID; }
-    // sample rows (grid coordinates) whose footprint can touch output rows [rb, re)
-    int32_t srow0 = std::max(rb, 0), srow1 = std::min(re + 4, g.NY);
-    if (single_pixel) {
-        const int32_t sx = single_pixel[0] - g.min_x, sy = single_pixel[1] - g.min_y;
+    u.rb = prm.row_begin; u.re = prm.row_end;
+    if (u.re <= u.rb) { u.rb = 0; u.re = prm.height; }
+    if (u.rb < 0 || u.re > prm.height) { err = "row band outside the film"; return PTRS_ERR_INVALID; }
+    u.srow0 = std::max(u.rb, 0); u.srow1 = std::min(u.re + 4, g.NY);
+    if (job.single_pixel) {
+        const int32_t sx = job.single_pixel[0] - g.min_x, sy = job.single_pixel[1] - g.min_y;
         if (sx < 0 || sx >= g.NX || sy < 0 || sy >= g.NY) { err = "pixel outside the sample bounds"; return PTRS_ERR_INVALID; }
-        if (!samples_out) { err = "null argument"; return PTRS_ERR_INVALID; }
-        srow0 = sy; srow1 = sy + 1;
+        if (!job.samples_out) { err = "null argument"; return PTRS_ERR_INVALID; }
+        u.srow0 = sy; u.srow1 = sy + 1;
     }
 
-    DSampler S;
-    S.matrices = be.sobol_matrices(); S.bytetab = be.sobol_bytetab(); S.nibtab = be.sobol_nibtab(); S.vdc = be.sobol_vdc(g.log2_res - 1); S.vdc_inv = be.sobol_vdc_inv(g.log2_res - 1);
-    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
-    S.kind = (uint32_t)prm.sampler; S.strat_dims = (uint32_t)prm.n_sampled_dimensions; S.strat1 = nullptr; S.strat2 = nullptr;
-    if (strat_dim) { // every tile's generator runs through the whole tile, whichever rows this call renders
-        int rc_t = be.strat_tables(g.NX, g.NY, strat_dim, S.strat_dims, &S.strat1, &S.strat2, err);
+    DSampler &S = u.S;
+    S = make_sampler(g, be.sobol_matrices(), be.sobol_bytetab(), be.sobol_nibtab(), be.sobol_vdc(g.log2_res - 1), be.sobol_vdc_inv(g.log2_res - 1));
+    S.kind = (uint32_t)prm.sampler; S.strat_dims = (uint32_t)prm.n_sampled_dimensions;
+    if (u.strat_dim) { // every tile's generator runs through the whole tile, whichever rows this call renders
+        int rc_t = be.strat_tables(g.NX, g.NY, u.strat_dim, S.strat_dims, &S.strat1, &S.strat2, err);
         if (rc_t != PTRS_OK) return rc_t;
     }
-    DCamera C;
-    std::memcpy(C.rot, cam.rot, 16); std::memcpy(C.trans, cam.trans, 12);
-    C.m00 = cam.m00; C.m11 = cam.m11; C.m22 = cam.m22; C.m23 = cam.m23;
-    std::memcpy(C.r2s, cam.raster_to_screen, 64); std::memcpy(C.dxc, cam.dx_camera, 12); std::memcpy(C.dyc, cam.dy_camera, 12);
-    DParams R;
-    std::memset(&R, 0, sizeof(R));
+    u.C = make_camera(cam);
+    DParams &R = u.R;
     R.max_depth = prm.max_depth; R.rr_threshold = prm.rr_threshold; R.rr_start_depth = prm.rr_start_depth; R.rr_enable = prm.rr_enable;
     R.NX = g.NX; R.NY = g.NY; R.W = prm.width; R.H = prm.height;
     R.inv_sqrt_spp = 1.0f / std::sqrt((float)g.spp);
     R.counters_on = (prm.flags & PTRS_FLAG_COUNTERS) ? 1u : 0u;
-    R.row_cost = row_cost;
+    R.row_cost = job.row_cost;
+    return PTRS_OK;
+}
+
+// How a band of `band_rows` sample rows x NX sample pixels x `ns` samples is cut into passes of at most `capacity` paths (capacity >= NX):
+// whole-band passes of equal sample chunks where a sample of the band fits, else one sample index per pass and equal row blocks.  With
+// several lanes (and no paths_per_pass given) the number of sample chunks is rounded up to a multiple of the lanes.
+// False: "pass too large" (a pass's path count must stay below 2^32 - 1).
+struct PassPlan { uint64_t rows_per_pass, samples_per_pass, max_paths /* of the largest pass */; };
+inline bool plan_passes(uint64_t band_rows, uint64_t NX, uint64_t ns, uint64_t capacity, uint32_t n_lanes, bool paths_per_pass_given, PassPlan &p) {
+    if (band_rows * NX <= capacity) {
+        p.rows_per_pass = band_rows;
+        // balance the sample chunks: n passes of (almost) equal size instead of full passes plus a small tail
+        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(ns, capacity / (band_rows * NX)));
+        uint64_t n_chunks = (ns + spp_max - 1) / spp_max;
+        if (n_lanes > 1 && !paths_per_pass_given && ns >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes; // an even number of equal sample chunks
+        p.samples_per_pass = (ns + n_chunks - 1) / n_chunks;
+    } else {
+        p.samples_per_pass = 1;
+        const uint64_t rows_max = std::max<uint64_t>(1, capacity / NX);
+        const uint64_t n_chunks = (band_rows + rows_max - 1) / rows_max;
+        p.rows_per_pass = (band_rows + n_chunks - 1) / n_chunks;
+    }
+    p.max_paths = p.rows_per_pass * NX * p.samples_per_pass;
+    return p.max_paths < 0xffffffffull;
+}
+
+template <class BE>
+int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm, const RenderJob &job, std::string &err) {
+    using clock = std::chrono::steady_clock;
+    const bool *kinds_present = sc_host_feat.kinds_present;
+    auto t_begin = clock::now();
+    RenderSetup u;
+    int rc = render_setup(be, bvh_depth, cam, prm, job, u, err);
+    if (rc != PTRS_OK) return rc;
+    const SampleGrid &g = u.g;
+    const uint32_t sb = u.sb, se = u.se, ns = se - sb;
+    const int32_t rb = u.rb, re = u.re, srow0 = u.srow0, srow1 = u.srow1;
+    DParams R = u.R;
 
     // ---- pass planning ----------------------------------------------------------------------
     // Passes run on `be.lanes()` independent pipelines (own path state, queues and stream): while one pass is in the thin
     // tail of a kernel or waits for its next launch, the other pass's workgroups fill the machine (two concurrent
     // processes on one MI355X measured +18 % over one).  Film kernels are chained in pass order, so the film is formed
     // by exactly the same additions as with a single pipeline.
-    const uint32_t n_lanes = std::max(1u, be.lanes((uint64_t)(srow1 - srow0) * (uint64_t)g.NX * (uint64_t)ns, sc_host_feat.kinds_present, single_pixel != nullptr, ns)); // (the back end may choose by the size of the job: a range's job is its own samples)
+    const uint64_t band_rows = (uint64_t)(srow1 - srow0);
+    const uint32_t n_lanes = std::max(1u, be.lanes(band_rows * (uint64_t)g.NX * (uint64_t)ns, kinds_present, job.single_pixel != nullptr, ns)); // (the back end may choose by the size of the job: a range's job is its own samples)
     // up to 2^27 paths (~35 GB of path state) per lane: HBM (288 GB) is plentiful, launches and tails are not free.  The back
     // end bounds it by its share of the memory that is free right now, so the library stays embeddable beside other users.
-    uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, sc_host_feat.kinds_present)); // (2^27: a path slot is 27 bits of a NEE-queue entry, pt_scene.h)
+    uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, kinds_present)); // (2^27: a path slot is 27 bits of a NEE-queue entry, pt_scene.h)
     if (capacity < (uint64_t)g.NX) capacity = (uint64_t)g.NX;
-    if (single_pixel) capacity = std::max<uint64_t>(capacity, (uint64_t)g.NX * ns); // one pass: the pixel's spp paths (planned below as one row x all samples, launched as spp paths)
-    const uint64_t band_rows = (uint64_t)(srow1 - srow0);
-    uint64_t rows_per_pass, samples_per_pass;
-    if (band_rows * (uint64_t)g.NX <= capacity) {
-        rows_per_pass = band_rows;
-        // balance the sample chunks: n passes of (almost) equal size instead of full passes plus a small tail
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(ns, capacity / (band_rows * (uint64_t)g.NX)));
-        const uint64_t n_chunks = (ns + spp_max - 1) / spp_max;
-        samples_per_pass = (ns + n_chunks - 1) / n_chunks;
-    } else {
-        samples_per_pass = 1;
-        const uint64_t rows_max = std::max<uint64_t>(1, capacity / (uint64_t)g.NX);
-        const uint64_t n_chunks = (band_rows + rows_max - 1) / rows_max;
-        rows_per_pass = (band_rows + n_chunks - 1) / n_chunks;
-    }
-    if (n_lanes > 1 && band_rows * (uint64_t)g.NX <= capacity && !prm.paths_per_pass) { // an even number of equal sample chunks
-        const uint64_t spp_max = std::max<uint64_t>(1, std::min<uint64_t>(ns, capacity / (band_rows * (uint64_t)g.NX)));
-        uint64_t n_chunks = (ns + spp_max - 1) / spp_max;
-        if (ns >= n_lanes) n_chunks = ((n_chunks + n_lanes - 1) / n_lanes) * n_lanes;
-        samples_per_pass = (ns + n_chunks - 1) / n_chunks;
-    }
-    const uint64_t max_paths = rows_per_pass * (uint64_t)g.NX * samples_per_pass;
-    if (max_paths >= 0xffffffffull) { err = "pass too large"; return PTRS_ERR_INVALID; }
+    if (job.single_pixel) capacity = std::max<uint64_t>(capacity, (uint64_t)g.NX * ns); // one pass: the pixel's spp paths (planned below as one row x all samples, launched as spp paths)
+    PassPlan plan;
+    if (!plan_passes(band_rows, (uint64_t)g.NX, ns, capacity, n_lanes, prm.paths_per_pass != 0, plan)) { err = "pass too large"; return PTRS_ERR_INVALID; }
+    const uint64_t rows_per_pass = plan.rows_per_pass, samples_per_pass = plan.samples_per_pass, max_paths = plan.max_paths;
 
     const uint32_t fixed_iters = (uint32_t)prm.max_depth + 1u; // li() runs at most max_depth+1 scene queries (Q7)
     const uint32_t max_iters = fixed_iters + 64u;              // head-room for null-BSDF skips (bounces -= 1)
     const int feat = scene_features(sc_host_feat), feat_trace = scene_trace_features(sc_host_feat);
-    int rc = be.begin(sc, S, C, (uint32_t)max_paths, max_iters + 1u, bvh_depth, prm.flags, feat, feat_trace, err);
+    rc = be.begin(sc, u.S, u.C, (uint32_t)max_paths, max_iters + 1u, bvh_depth, prm.flags, feat, feat_trace, err);
     if (rc != PTRS_OK) return rc;
 
     PtrsStats st;
@@ -286,9 +329,9 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             if (it == max_iters && be.read_count(it, Q_EXT) != 0) null_skip_overrun = true; // paths still alive: never dropped silently
         }
         pd.it = it;
-        if (pd.y1 > pd.y0 && film) be.film(film, pd.y0, pd.y1); // ordered after the previous pass's film kernel, whichever lane ran it
-        if (pd.y1 > pd.y0 && film_half) be.film(film_half, pd.y0, pd.y1); // (the same pass into the half film: its own running sums, in the same order)
-        if (samples_out) be.export_samples(samples_out);
+        if (pd.y1 > pd.y0 && job.film) be.film(job.film, pd.y0, pd.y1); // ordered after the previous pass's film kernel, whichever lane ran it
+        if (pd.y1 > pd.y0 && job.film_half) be.film(job.film_half, pd.y0, pd.y1); // (the same pass into the half film: its own running sums, in the same order)
+        if (job.samples_out) be.export_samples(job.samples_out);
         pd.open = false;
     };
     auto finish = [&](uint32_t lane) { // collect the counters of the pass a lane ran last (waits for that lane only)
@@ -308,7 +351,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
         // progressive render: the pass's rows are published here, when its lane is waited for anyway (before the lane's next pass, or at
         // the end), not right behind its launch -- the passes on the other lanes keep running meanwhile.  Passes finish in launch order
         // (their film kernels are chained), so the callbacks arrive in pass order.
-        if (progress && progress->fn && pd.y1 > pd.y0) { be.publish_rows(film, pd.y0, pd.y1); progress->fn(progress->user, pd.pass_no + 1u, n_passes_total, pd.y0, pd.y1); }
+        if (job.progress && job.progress->fn && pd.y1 > pd.y0) { be.publish_rows(job.film, pd.y0, pd.y1); job.progress->fn(job.progress->user, pd.pass_no + 1u, n_passes_total, pd.y0, pd.y1); }
         pd.active = false;
     };
     uint32_t pass_no = 0;
@@ -323,15 +366,15 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             be.select(lane);
             R.row0 = r0; R.row1 = r1; R.s0 = s0; R.s1 = s1;
             R.n_paths = (uint32_t)(r1 - r0) * (uint32_t)g.NX * (s1 - s0);
-            if (single_pixel) { R.pixel_mode = 1; R.pix_sx = single_pixel[0] - g.min_x; R.pix_sy = single_pixel[1] - g.min_y; R.n_paths = s1 - s0; }
+            if (job.single_pixel) { R.pixel_mode = 1; R.pix_sx = job.single_pixel[0] - g.min_x; R.pix_sy = job.single_pixel[1] - g.min_y; R.n_paths = s1 - s0; }
             be.pass_begin(R);
             be.generate();
             uint32_t it = 0;
-            if (dump) { // (test / bench hook: nothing is rendered beyond the rounds before the dump)
-                for (; it < dump->round && it < max_iters; ++it) round(it);
-                be.dump_rays(it, *dump);
+            if (job.dump) { // (test / bench hook: nothing is rendered beyond the rounds before the dump)
+                for (; it < job.dump->round && it < max_iters; ++it) round(it);
+                be.dump_rays(it, *job.dump);
                 be.end(st);
-                if (stats) *stats = st;
+                if (job.stats) *job.stats = st;
                 return PTRS_OK;
             }
             // Rounds as three launches each while the pass is thick; from the round the back end names (gfx950: where its survival profile
@@ -344,7 +387,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             // output rows touched by sample rows [r0, r1): pixel row = min_y + sample row, +-2
             const int32_t y0 = std::max(rb, g.min_y + r0 - 2), y1 = std::min(re, g.min_y + r1 - 1 + 2 + 1);
             pending[lane].active = true; pending[lane].it = it; pending[lane].n_paths = R.n_paths; pending[lane].pass_no = pass_no;
-            pending[lane].y0 = (single_pixel || y1 <= y0) ? 0 : y0; pending[lane].y1 = (single_pixel || y1 <= y0) ? 0 : y1;
+            pending[lane].y0 = (job.single_pixel || y1 <= y0) ? 0 : y0; pending[lane].y1 = (job.single_pixel || y1 <= y0) ? 0 : y1;
             pending[lane].open = true;
             if (!spare_rounds) close_pass(lane); // nothing to ask: the film kernel follows the rounds at once
         }
@@ -355,14 +398,22 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     if (null_skip_overrun) st.error_flags |= PTRS_ERRFLAG_NULL_SKIPS;
     st.bvh_nodes = sc.n_nodes; st.bvh_max_depth = bvh_depth;
     st.ms_total = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();
-    if (stats) *stats = st;
+    if (job.stats) *job.stats = st;
     if (st.error_flags & PTRS_ERRFLAG_SOBOL_DIM) {
-        err = strat_dim ? "stratified sampler: a path drew past n_sampled_dimensions (null-BSDF skips lengthen paths beyond max_depth, Q7); the reference would continue from the tile's generator in path order, which a wavefront cannot reproduce"
+        err = u.strat_dim ? "stratified sampler: a path drew past n_sampled_dimensions (null-BSDF skips lengthen paths beyond max_depth, Q7); the reference would continue from the tile's generator in path order, which a wavefront cannot reproduce"
                         : "sobol sampler can only sample up to 1024 dimensions (sobol.rs:177-183): max_depth is too large for this scene";
         return PTRS_ERR_UNSUPPORTED;
     }
     if (st.error_flags & PTRS_ERRFLAG_NULL_SKIPS) { err = "paths still alive after max_depth + 65 rounds of null-BSDF skips (integrator.rs:434-439)"; return PTRS_ERR_UNSUPPORTED; }
     return PTRS_OK;
+}
+
+// render_impl's positional form from before RenderJob, forwarded: not called in this tree, kept (deprecated) for twins written against it.
+template <class BE>
+[[deprecated("fill a RenderJob")]] int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm, v4 *film, float *samples_out, PtrsStats *stats, std::string &err,
+                const RenderProgress *progress = nullptr, const RayDump *dump = nullptr, const int32_t *single_pixel = nullptr, uint32_t *row_cost = nullptr, const uint32_t *sample_range = nullptr, v4 *film_half = nullptr) {
+    const RenderJob job{film, film_half, samples_out, stats, progress, dump, single_pixel, row_cost, sample_range}; // (RenderJob's member order)
+    return render_impl(be, sc, sc_host_feat, bvh_depth, cam, prm, job, err);
 }
 
 } // namespace pt

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1539,18 +1540,65 @@ __global__ __launch_bounds__(BLOCK) void k_probe_surface(DScene sc, uint32_t pri
 }
 
 // ---- device buffers ---------------------------------------------------------------------------------
+// Owns its block: the destructor frees it, so a scene, a denoiser or an entry point's locals need no release list and an early return
+// leaks nothing.  (Objects of static lifetime must therefore not hold one by value: see g_sobol.)
 struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t n) {
         if (n <= bytes) return PTRS_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
+        release();
         HIPCHK(hipMalloc(&p, n));
         bytes = n;
         return PTRS_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
+
+// ---- what every entry point asks first --------------------------------------------------------------
+int require_device(int *n_out = nullptr) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
+    if (n_out) *n_out = ndev;
+    return PTRS_OK;
+}
+int select_device(int32_t ordinal) {
+    int ndev = 0, rc = require_device(&ndev);
+    if (rc != PTRS_OK) return rc;
+    if (ordinal < 0 || ordinal >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
+    HIPCHK(hipSetDevice(ordinal));
+    return PTRS_OK;
+}
+
+// The rows of a host film that travel: only those of the band (rows outside [row_begin, row_end) are untouched: concurrent renders of
+// disjoint bands into one host film, one per device, do not step on each other).  off / px: the band's first pixel and its pixels.
+struct RowBand { size_t off = 0, px = 0; };
+int row_band(const PtrsRenderParams &prm, RowBand &b) {
+    int32_t rb = prm.row_begin, re = prm.row_end;
+    if (re <= rb) { rb = 0; re = prm.height; }
+    if (rb < 0 || re > prm.height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
+    b.off = (size_t)rb * (size_t)prm.width; b.px = (size_t)(re - rb) * (size_t)prm.width;
+    return PTRS_OK;
+}
+// a whole-film device copy in `buf` with the band of the host film in it / the band back into the host film
+int stage_in(DevBuf &buf, const PtrsRenderParams &prm, const RowBand &b, const PtrsFilmPixel *host) {
+    int rc = buf.ensure((size_t)prm.width * (size_t)prm.height * sizeof(PtrsFilmPixel));
+    if (rc != PTRS_OK) return rc;
+    HIPCHK(hipMemcpy((PtrsFilmPixel *)buf.p + b.off, host + b.off, b.px * sizeof(PtrsFilmPixel), hipMemcpyHostToDevice));
+    return PTRS_OK;
+}
+int stage_out(const DevBuf &buf, const RowBand &b, PtrsFilmPixel *host) {
+    HIPCHK(hipMemcpy(host + b.off, (const PtrsFilmPixel *)buf.p + b.off, b.px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
+    return PTRS_OK;
+}
+// bytes of a per-sample export: every sample of the whole render (total_spp), `floats` each
+size_t sample_buffer_bytes(const PtrsRenderParams &prm, size_t floats) {
+    const SampleGrid g = make_sample_grid(prm.width, prm.height, prm.spp);
+    return (size_t)g.NX * (size_t)g.NY * (size_t)total_spp(prm) * floats * sizeof(float);
+}
 
 template <class T> int upload(DevBuf &b, const std::vector<T> &v) {
     size_t n = v.size() * sizeof(T);
@@ -1566,6 +1614,8 @@ struct SobolDevice { // one copy per device
     uint32_t stride = 52;
 };
 std::mutex g_mu;
+// Raw pointers, never deleted: at process exit the HIP runtime may be gone before the statics' destructors run, and an owning DevBuf
+// would then call hipFree into it.
 std::vector<SobolDevice *> g_sobol;
 
 int get_sobol(int device, SobolDevice **out) {
@@ -1576,34 +1626,31 @@ int get_sobol(int device, SobolDevice **out) {
     uint32_t hdr[6]; std::memcpy(hdr, b + 8, 24);
     const size_t nmat = (size_t)hdr[0] * hdr[1], stride = hdr[4];
     const unsigned char *pm = b + 32, *pv = pm + nmat * 4 + 52 * 4, *pvi = pv + (size_t)hdr[2] * stride * 8;
-    auto *s = new SobolDevice(); s->device = device; s->stride = (uint32_t)stride;
+    std::unique_ptr<SobolDevice> s(new SobolDevice()); // (freed on every failure below; handed to g_sobol only when complete)
+    s->device = device; s->stride = (uint32_t)stride;
     int rc;
     const size_t mat_pad = 16 * 52 * 4; // a path that overruns the 1024 dimensions reads up to 8 rows past the table before its kernel raises PTRS_ERRFLAG_SOBOL_DIM
-    if ((rc = s->matrices.ensure(nmat * 4 + mat_pad)) != PTRS_OK || (rc = s->vdc.ensure((size_t)hdr[2] * stride * 8)) != PTRS_OK || (rc = s->vdc_inv.ensure((size_t)hdr[3] * stride * 8)) != PTRS_OK) { delete s; return rc; }
+    if ((rc = s->matrices.ensure(nmat * 4 + mat_pad)) != PTRS_OK || (rc = s->vdc.ensure((size_t)hdr[2] * stride * 8)) != PTRS_OK || (rc = s->vdc_inv.ensure((size_t)hdr[3] * stride * 8)) != PTRS_OK) return rc;
     HIPCHK(hipMemset(s->matrices.p, 0, nmat * 4 + mat_pad));
     HIPCHK(hipMemcpy(s->matrices.p, pm, nmat * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->vdc.p, pv, (size_t)hdr[2] * stride * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->vdc_inv.p, pvi, (size_t)hdr[3] * stride * 8, hipMemcpyHostToDevice));
-    {
-        SobolTablesHost T; T.matrices.resize(nmat); std::memcpy(T.matrices.data(), pm, nmat * 4);
-        std::vector<uint32_t> bt; build_sobol_bytetab(T, bt);
-        if ((rc = s->bytetab.ensure(bt.size() * 4)) != PTRS_OK) { delete s; return rc; }
-        HIPCHK(hipMemcpy(s->bytetab.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
-        // nibtab[dim][n][v] = XOR of the matrix columns 4n + j over the set bits j of v: the form the shade kernels stage into
-        // LDS (64 B per index nibble and dimension; the byte tables above would need 1 KB)
-        std::vector<uint32_t> nt((size_t)1024 * SOBOL_NIBBLES * 16, 0u);
-        for (uint32_t d = 0; d < 1024; ++d)
-            for (uint32_t n = 0; n < (uint32_t)SOBOL_NIBBLES; ++n)
-                for (uint32_t v = 0; v < 16; ++v) {
-                    uint32_t x = 0;
-                    for (uint32_t j = 0; j < 4; ++j) if ((v >> j) & 1u) { const uint32_t col = 4 * n + j; if (col < 52) x ^= T.matrices[(size_t)d * 52 + col]; }
-                    nt[((size_t)d * SOBOL_NIBBLES + n) * 16 + v] = x;
-                }
-        if ((rc = s->nibtab.ensure(nt.size() * 4)) != PTRS_OK) { delete s; return rc; }
-        HIPCHK(hipMemcpy(s->nibtab.p, nt.data(), nt.size() * 4, hipMemcpyHostToDevice));
-    }
-    g_sobol.push_back(s);
-    *out = s;
+    SobolTablesHost T; T.matrices.resize(nmat); std::memcpy(T.matrices.data(), pm, nmat * 4);
+    std::vector<uint32_t> bt; build_sobol_bytetab(T, bt);
+    if ((rc = upload(s->bytetab, bt)) != PTRS_OK) return rc;
+    // nibtab[dim][n][v] = XOR of the matrix columns 4n + j over the set bits j of v: the form the shade kernels stage into
+    // LDS (64 B per index nibble and dimension; the byte tables above would need 1 KB)
+    std::vector<uint32_t> nt((size_t)1024 * SOBOL_NIBBLES * 16, 0u);
+    for (uint32_t d = 0; d < 1024; ++d)
+        for (uint32_t n = 0; n < (uint32_t)SOBOL_NIBBLES; ++n)
+            for (uint32_t v = 0; v < 16; ++v) {
+                uint32_t x = 0;
+                for (uint32_t j = 0; j < 4; ++j) if ((v >> j) & 1u) { const uint32_t col = 4 * n + j; if (col < 52) x ^= T.matrices[(size_t)d * 52 + col]; }
+                nt[((size_t)d * SOBOL_NIBBLES + n) * 16 + v] = x;
+            }
+    if ((rc = upload(s->nibtab, nt)) != PTRS_OK) return rc;
+    g_sobol.push_back(s.get());
+    *out = s.release();
     return PTRS_OK;
 }
 
@@ -1633,16 +1680,7 @@ struct PtrsScene {
     hipEvent_t lane_ev[MAX_LANES] = {};      // film-done per lane
     std::vector<hipEvent_t> ev_pool;
     int n_cu = 256;
-    ~PtrsScene() {
-        for (auto &b : {&stack_spill, &nodes2, &nodes4, &nodes, &tris, &shade, &mats, &texs, &levels, &texdata, &lights, &distdata, &inf, &stats, &table, &film_tmp, &samples_tmp, &strat1, &strat2, &row_cost, &half_tmp, &cv_tiles, &cv_summary}) b->release();
-        for (auto &b : aov_film_tmp) b.release();
-        for (auto &b : aov_band) b.release();
-        aov_band_pfilm.release();
-        aov_samples_tmp.release();
-        for (auto &b : counts) b.release();
-        for (auto &b : totals) b.release();
-        for (auto &b : tickets) b.release();
-        for (auto &l : ws) for (auto &b : l) b.release();
+    ~PtrsScene() { // (the buffers free themselves)
         for (auto st : lane_stream) if (st) (void)hipStreamDestroy(st);
         for (auto e : lane_ev) if (e) (void)hipEventDestroy(e);
         for (auto e : ev_pool) (void)hipEventDestroy(e);
@@ -1656,10 +1694,18 @@ struct PtrsDenoiser {
     int32_t W = 0, H = 0;
     DevBuf ws;       // 64 bytes per pixel: colour ping, colour pong, guide, albedo
     DevBuf stage[5]; // ptrs_denoise: the host films' device copies (beauty, the three planes, out)
-    ~PtrsDenoiser() { ws.release(); for (auto &b : stage) b.release(); }
 };
 
 namespace {
+
+// A scene whose tree is deeper than its LDS stack column (spill_lane_elems != 0) runs the OVF = true kernels on its spill block.  Without
+// the block (an allocation in HipBackend::begin failed) it is refused: the OVF = false kernels would push past the column, into the
+// LDS copy of the nodes.  The next render allocates again.
+int require_spill(const PtrsScene *ps) {
+    if (ps->spill_lane_elems == 0 || ps->spill.p) return PTRS_OK;
+    g_err = "the scene has lost its traversal stack spill columns (an earlier allocation failed); a render allocates them again";
+    return PTRS_ERR_DEVICE;
+}
 
 struct HipBackend {
     PtrsScene *ps; hipStream_t stream; SobolDevice *sob;
@@ -1719,6 +1765,7 @@ struct HipBackend {
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 1ull << 27;
         size_t held = 0;
         for (auto &l : ps->ws) for (auto &b : l) held += b.bytes;
+        held += ps->stack_spill.bytes;
         uint32_t nk = 0; for (int k = 0; k < 7; ++k) nk += kinds[k] ? 1u : 0u;
         const double per_path = (17.0 + (ps->H.inf_lights.empty() ? 0.0 : 2.0)) * 16.0 + 8.0 + 4.0 + 3.0 * 4.0 + nk * 8.0; // 15 vectors in queue order (ray, throughput double-buffered), 2 by path slot, the presampled light sample, the film position, pre_z, three queues, the shade queues
         const double budget = (double)(fr + held) * (double)opt.workspace_pct / 100.0 / (double)std::max(1, share); // `share` renders divide this device's memory (ptrs_render_multi)
@@ -1739,6 +1786,8 @@ struct HipBackend {
     const uint32_t *sobol_matrices() { return (const uint32_t *)sob->matrices.p; }
     const uint32_t *sobol_bytetab() { return (const uint32_t *)sob->bytetab.p; }
     const uint32_t *sobol_nibtab() { return (const uint32_t *)sob->nibtab.p; }
+    const uint64_t *sobol_vdc(uint32_t row) { return (const uint64_t *)sob->vdc.p + (size_t)row * sob->stride; }
+    const uint64_t *sobol_vdc_inv(uint32_t row) { return (const uint64_t *)sob->vdc_inv.p + (size_t)row * sob->stride; }
     int strat_tables(int32_t NX, int32_t NY, uint32_t dim_ps, uint32_t n_dims, const float **t1, const float **t2, std::string &err) {
         const size_t n = (size_t)NX * (size_t)NY * n_dims * dim_ps * dim_ps;
         size_t fr = 0, tot = 0;
@@ -1751,8 +1800,6 @@ struct HipBackend {
         *t1 = (const float *)ps->strat1.p; *t2 = (const float *)ps->strat2.p;
         return PTRS_OK;
     }
-    const uint64_t *sobol_vdc(uint32_t row) { return (const uint64_t *)sob->vdc.p + (size_t)row * sob->stride; }
-    const uint64_t *sobol_vdc_inv(uint32_t row) { return (const uint64_t *)sob->vdc_inv.p + (size_t)row * sob->stride; }
 
     hipEvent_t ev() {
         if (ev_next == ps->ev_pool.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { rc = PTRS_ERR_DEVICE; return nullptr; } ps->ev_pool.push_back(e); }
@@ -1790,8 +1837,8 @@ struct HipBackend {
     // kernel's, where one number serves both).  A launch of W resident waves works through G equal segments in ceil(G / W) rounds, the last
     // one only partly filled: at G / W = 2.67 a third of the waves idle for the last third of every kernel (utilisation G / W / ceil(G / W) =
     // 0.89; the same at 5.33), at a whole ratio none do.
-    template <int FEAT_T> uint32_t whole_rounds(uint32_t target) {
-        const uint32_t we = resident_grid(pick_extend<FEAT_T>(vote, ps->spill.p != nullptr)) * WAVES;
+    uint32_t whole_rounds(uint32_t target) {
+        const uint32_t we = resident_grid(pick_extend(feat_trace, vote, ps->spill.p != nullptr)) * WAVES;
         uint32_t ws = 0;
         for (int k = 0; k < 6 && !ws; ++k) if (ps->H.kinds_present[k]) ws = resident_grid(shade_fn(k)) * WAVES;
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
@@ -1802,28 +1849,36 @@ struct HipBackend {
     }
     uint32_t *ticket(uint32_t it, int which) { return Q.tickets + ((size_t)it * Q_STRIDE + (size_t)which) * TK_LAUNCH_WORDS; }
 
-    int begin(const DScene &sc_, const DSampler &S_, const DCamera &C_, uint32_t capacity, uint32_t count_rows, uint32_t bvh_depth, uint32_t flags_, int feat_, int feat_trace_, std::string &err) {
-        sc = sc_; S = S_; C = C_; cap = capacity; rows = count_rows; depth = bvh_depth; flags = flags_; feat = feat_; feat_trace = feat_trace_;
-        plan_segments(capacity);
+    // How the traversal kernels of this scene run: phase voting, idle-lane thresholds, geometry source.  begin() and ptrs_trace_bench both
+    // ask here, so the bench launches the kernel a frame launches.
+    void traversal_policy(int feat_trace_) {
+        feat_trace = feat_trace_;
         // phase voting: quad-node scenes gain in both traversal kernels; on the LDS pair form a step is cheap enough that the vote's
         // own instructions eat the gain in the connect kernel (+20 %), the extension kernel keeps 4 % (A/B on MI355X)
         vote = opt.vote >= 0 ? opt.vote != 0 : true;
-        vote_connect = opt.vote >= 0 ? opt.vote == 1 : sc.n_nodes4 != 0;
+        vote_connect = opt.vote >= 0 ? opt.vote == 1 : ps->sc.n_nodes4 != 0;
         // idle-lane threshold: a voting wave comes back for retire / refill in batches, and with the cheap steps of the kernels without
         // alpha masks a bigger batch pays (Cornell extend 88.8 -> 85.7 ms, colonnade connect 38.2 -> 36.4 ms at 32); the full-feature
         // kernels (classroom) are better off at 16 (extend 227 vs 233 ms).  0 = no refill while a lane still works (threshold 64).
         refill = (uint32_t)(opt.refill > 0 ? opt.refill : (opt.refill == 0 ? 64 : ((vote && feat_trace == FEAT_SIMPLE) ? 32 : 16)));
         refill_connect = (uint32_t)(opt.refill_connect > 0 ? opt.refill_connect : (opt.refill_connect == 0 ? 64 : ((vote_connect && feat_trace == FEAT_SIMPLE) ? 32 : 16)));
-        geom4 = sc.n_nodes4 ? 0xffffffffu : LN_V4 * sc.n_nodes2 + 9u * sc.n_prims; // quad form: global kernels; pair form: fits the LDS staging area by construction (pt_host_scene.h)
+        geom4 = ps->sc.n_nodes4 ? 0xffffffffu : LN_V4 * ps->sc.n_nodes2 + 9u * ps->sc.n_prims; // quad form: global kernels; pair form: fits the LDS staging area by construction (pt_host_scene.h)
+    }
+    int begin(const DScene &sc_, const DSampler &S_, const DCamera &C_, uint32_t capacity, uint32_t count_rows, uint32_t bvh_depth, uint32_t flags_, int feat_, int feat_trace_, std::string &err) {
+        sc = sc_; S = S_; C = C_; cap = capacity; rows = count_rows; depth = bvh_depth; flags = flags_; feat = feat_;
+        plan_segments(capacity);
+        traversal_policy(feat_trace_);
         for (int k = 0; k < 7; ++k) if (ps->H.kinds_present[k]) kinds_mask |= 1u << k;
         grid_max = ps->n_cu * 8 * (opt.grid_mult ? opt.grid_mult : 8);
-        if (opt.persist && opt.whole_rounds) grid_max = (int)(feat_trace == FEAT_FULL ? whole_rounds<FEAT_FULL>((uint32_t)grid_max) : (feat_trace == FEAT_IMG_ENV ? whole_rounds<FEAT_IMG_ENV>((uint32_t)grid_max) : whole_rounds<FEAT_SIMPLE>((uint32_t)grid_max)));
+        if (opt.persist && opt.whole_rounds) grid_max = (int)whole_rounds((uint32_t)grid_max);
         const size_t n16 = (size_t)cap * 16, n4 = ((size_t)cap + ((size_t)grid_max + 1) * 64) * 4; // queues: G segments of whole 64-entry chunks
         if ((rc = ps->stats.ensure(CNT_NUM * 8)) != PTRS_OK || (rc = ps->table.ensure(1024)) != PTRS_OK) { err = g_err; return rc; }
         if (ps->spill_lane_elems) { // the traversal stacks' global columns: one set per pipeline lane of THIS render (concurrent lanes must not share columns)
-            if ((rc = ps->stack_spill.ensure(ps->spill_lane_elems * n_lanes * sizeof(unsigned long long))) != PTRS_OK) { err = g_err + " (traversal stack spill columns)"; return rc; }
-            ps->spill.p = (unsigned long long *)ps->stack_spill.p;
+            rc = ps->stack_spill.ensure(ps->spill_lane_elems * n_lanes * sizeof(unsigned long long));
+            ps->spill.p = (unsigned long long *)ps->stack_spill.p; // (null after a failed allocation, never the freed block: require_spill then refuses the scene until a render gets its columns)
+            if (rc != PTRS_OK) { err = g_err + " (traversal stack spill columns)"; return rc; }
         }
+        if ((rc = require_spill(ps)) != PTRS_OK) { err = g_err; return rc; }
         for (uint32_t l = 0; l < n_lanes && n_lanes > 1; ++l) {
             if (l > 0 && !ps->lane_stream[l] && hipStreamCreateWithFlags(&ps->lane_stream[l], hipStreamNonBlocking) != hipSuccess) { err = "cannot create a pipeline stream"; return PTRS_ERR_DEVICE; }
             if (!ps->lane_ev[l] && hipEventCreateWithFlags(&ps->lane_ev[l], hipEventDisableTiming) != hipSuccess) { err = "cannot create pipeline events"; return PTRS_ERR_DEVICE; }
@@ -1884,32 +1939,50 @@ struct HipBackend {
 #define PTRS_PICK(K, D, O, GE) (v ? (TravFn)K<FEAT, D, O, GE, true> : (TravFn)K<FEAT, D, O, GE, false>)
 #define PTRS_PICK_ALL(K) (ps->stack_lds == 9 ? PTRS_PICK(K, 9, false, LDS9_V4) : ps->stack_lds == 8 ? (geom4 <= 640 ? (ovf ? PTRS_PICK(K, 8, true, 640) : PTRS_PICK(K, 8, false, 640)) : geom4 <= 1536 ? (ovf ? PTRS_PICK(K, 8, true, 1536) : PTRS_PICK(K, 8, false, 1536)) : (ovf ? PTRS_PICK(K, 8, true, 0) : PTRS_PICK(K, 8, false, 0))) \
                                               : (ovf ? PTRS_PICK(K, 16, true, 0) : PTRS_PICK(K, 16, false, 0)))
-    template <int FEAT> TravFn pick_extend(bool v, bool ovf) { return PTRS_PICK_ALL(k_extend_rf); }
-    template <int FEAT> TravFn pick_connect(bool v, bool ovf) { return PTRS_PICK_ALL(k_connect_rf); }
+    // (fused_epilogue / fused_resolve = 0: the segment's epilogue / MIS resolve run as kernels of their own)
+    typedef void (*EpilogueFn)(DParams, DScene, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *);
+    struct ConnectFns { TravFn connect; void (*resolve)(DScene, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t *); };
+    template <int FEAT> TravFn pick_extend_t(bool v, bool ovf) { return PTRS_PICK_ALL(k_extend_rf); }
+    template <int FEAT> ConnectFns pick_connect_t(bool v, bool ovf) { return ConnectFns{PTRS_PICK_ALL(k_connect_rf), k_resolve<FEAT>}; }
 #undef PTRS_PICK_ALL
 #undef PTRS_PICK
+    // The one place where feat_trace becomes a template argument.  WHERE these functions stand is measured: the code object lists the template
+    // kernels in the order non-template code first names them, and epilogue_fn, pick_connect (with its resolve kernel) and pick_extend (defined
+    // behind ptrs_trace_rays) keep the earlier order.  Side by side here, the same kernels lie elsewhere: classroom's shade ran 0.8 % slower.
+    EpilogueFn epilogue_fn() const {
+        static const EpilogueFn by_feat[3] = {k_epilogue<FEAT_FULL>, k_epilogue<FEAT_IMG_ENV>, k_epilogue<FEAT_SIMPLE>};
+        return by_feat[feat_trace == FEAT_FULL ? 0 : feat_trace == FEAT_IMG_ENV ? 1 : 2];
+    }
+    ConnectFns pick_connect(int ft, bool v, bool ovf) { return ft == FEAT_FULL ? pick_connect_t<FEAT_FULL>(v, ovf) : ft == FEAT_IMG_ENV ? pick_connect_t<FEAT_IMG_ENV>(v, ovf) : pick_connect_t<FEAT_SIMPLE>(v, ovf); }
+    TravFn pick_extend(int ft, bool v, bool ovf);
     StackSpill lane_spill() { StackSpill sp = ps->spill; if (sp.p) sp.p += (size_t)cur * ps->spill_lane_elems; return sp; } // this lane's columns
 
-    template <int FEAT> void extend_t(uint32_t it) {
+    void extend(uint32_t it) {
+        t0(T_EXTEND);
         const StackSpill sp = lane_spill();
         const uint32_t epi_mask = opt.fused_epilogue ? kinds_mask : 0u; // non-zero: the kernel runs its segment's epilogue behind its last ray
-        const TravFn fn = pick_extend<FEAT>(vote, sp.p != nullptr);
+        const TravFn fn = pick_extend(feat_trace, vote, sp.p != nullptr);
         hipLaunchKernelGGL(fn, dim3(persistent_grid(fn, T_EXTEND)), dim3(BLOCK), 0, stream, R, sc, sp, P, Q, it, seg_cap, refill, epi_mask, G, ticket(it, TK_EXTEND));
-        if (epi_mask) return;
-        t1(); t0(T_AUX); // the traversal span ends here: the epilogue is shading-side work
-        hipLaunchKernelGGL((k_epilogue<FEAT>), dim3(persistent_grid(k_epilogue<FEAT>, T_AUX)), dim3(BLOCK), 0, stream, R, sc, P, Q, it, kinds_mask, seg_cap, G, ticket(it, TK_EPILOGUE));
+        if (!epi_mask) {
+            t1(); t0(T_AUX); // the traversal span ends here: the epilogue is shading-side work
+            const EpilogueFn ep = epilogue_fn();
+            hipLaunchKernelGGL(ep, dim3(persistent_grid(ep, T_AUX)), dim3(BLOCK), 0, stream, R, sc, P, Q, it, kinds_mask, seg_cap, G, ticket(it, TK_EPILOGUE));
+        }
+        t1();
     }
-    void extend(uint32_t it) { t0(T_EXTEND); if (feat_trace == FEAT_FULL) extend_t<FEAT_FULL>(it); else if (feat_trace == FEAT_IMG_ENV) extend_t<FEAT_IMG_ENV>(it); else extend_t<FEAT_SIMPLE>(it); t1(); }
-    template <int FEAT> void connect_t(uint32_t it) {
+    void connect(uint32_t it) {
+        t0(T_CONNECT);
         const StackSpill sp = lane_spill();
         const uint32_t fused = (opt.fused_epilogue && opt.fused_resolve) ? 1u : 0u;
-        const TravFn fn = pick_connect<FEAT>(vote_connect, sp.p != nullptr);
+        const ConnectFns cf = pick_connect(feat_trace, vote_connect, sp.p != nullptr);
+        const TravFn fn = cf.connect;
         hipLaunchKernelGGL(fn, dim3(persistent_grid(fn, T_CONNECT)), dim3(BLOCK), 0, stream, R, sc, sp, P, Q, it, seg_cap, refill_connect, fused, G, ticket(it, TK_CONNECT));
-        if (fused) return;
-        t1(); t0(T_AUX);
-        hipLaunchKernelGGL((k_resolve<FEAT>), dim3(persistent_grid(k_resolve<FEAT>, T_AUX)), dim3(BLOCK), 0, stream, sc, P, Q, it, seg_cap, G, ticket(it, TK_RESOLVE));
+        if (!fused) {
+            t1(); t0(T_AUX);
+            hipLaunchKernelGGL(cf.resolve, dim3(persistent_grid(cf.resolve, T_AUX)), dim3(BLOCK), 0, stream, sc, P, Q, it, seg_cap, G, ticket(it, TK_RESOLVE));
+        }
+        t1();
     }
-    void connect(uint32_t it) { t0(T_CONNECT); if (feat_trace == FEAT_FULL) connect_t<FEAT_FULL>(it); else if (feat_trace == FEAT_IMG_ENV) connect_t<FEAT_IMG_ENV>(it); else connect_t<FEAT_SIMPLE>(it); t1(); }
     // The Sobol' dimensions a vertex of round `it` can draw: a path starts the round at dimension <= 3 + 8 it (two camera
     // dimensions, the skipped dimension 4, at most 8 per vertex before) and draws at most 9 further ones; the window staged
     // into LDS is the top of that range (paths below it -- long specular chains -- read the global tables).
@@ -2050,7 +2123,6 @@ struct HipBackend {
         uint32_t n = 0;
         if (hipMemcpyAsync(&n, cnt.p, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) rc = PTRS_ERR_DEVICE;
         *d.n_out = n < d.max_rays ? n : d.max_rays;
-        cnt.release();
     }
     // ---- first-hit feature planes (pt_aov.h): the values sit in path-state arrays of the shade / connect stages, which an AOV pass never runs
     bool aov_band = false; // band mode: the values go to arrays of the whole band instead
@@ -2130,21 +2202,33 @@ Options scene_options(const PtrsScene *ps) { // the process-wide knobs with this
     return o;
 }
 
-int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, v4 *film_dev, float *samples_dev, hipStream_t stream, PtrsStats *stats, const int32_t *single_pixel = nullptr,
-              const RenderProgress *progress = nullptr, PtrsFilmPixel *host_film = nullptr, int share = 1, const RayDump *dump = nullptr, uint32_t *row_cost_dev = nullptr,
-              const uint32_t *sample_range = nullptr, v4 *film_half_dev = nullptr) {
-    if (!ps || !cam || !prm || (!film_dev && !single_pixel && !row_cost_dev)) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+// What a render on the device is asked for: the job, and what only this back end knows.
+struct HipJob : RenderJob {
+    hipStream_t stream = nullptr;
+    PtrsFilmPixel *host_film = nullptr; // ptrs_render_progressive: the film the finished rows are published into
+    int share = 1;                      // renders that divide this device (ptrs_render_multi replicas)
+};
+// A render call's frame: the scene's device, a fresh back end on `stream` with the device's tables, run(be, err) -- render_impl or
+// render_aov_impl -- and the way its errors come back.
+template <class Run> int with_backend(PtrsScene *ps, const PtrsRenderParams *prm, hipStream_t stream, Run run) {
     HIPCHK(hipSetDevice(ps->device));
     HipBackend be;
-    be.ps = ps; be.stream = stream; be.opt = scene_options(ps); be.host_film = host_film; be.film_w = prm->width; be.share = share;
-    if (dump && be.opt.lanes == 0) be.opt.lanes = 1; // a ray dump is of the render's first pass: one lane gives that pass as many of the job's paths as memory holds
+    be.ps = ps; be.stream = stream; be.opt = scene_options(ps); be.film_w = prm->width;
     int rc = get_sobol(ps->device, &be.sob);
     if (rc != PTRS_OK) return rc;
     std::string err;
-    rc = render_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, film_dev, samples_dev, stats, err, progress, dump, single_pixel, row_cost_dev, sample_range, film_half_dev);
+    rc = run(be, err);
     if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
     if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
     return PTRS_OK;
+}
+int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, const HipJob &job) {
+    if (!ps || !cam || !prm || (!job.film && !job.single_pixel && !job.row_cost)) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    return with_backend(ps, prm, job.stream, [&](HipBackend &be, std::string &err) {
+        be.host_film = job.host_film; be.share = job.share;
+        if (job.dump && be.opt.lanes == 0) be.opt.lanes = 1; // a ray dump is of the render's first pass: one lane gives that pass as many of the job's paths as memory holds
+        return render_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, job, err);
+    });
 }
 
 // ptrs_render_aov / ptrs_render_aov_device: the checks that need no device, then that there is one
@@ -2153,22 +2237,11 @@ int aov_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderP
     if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
     for (uint32_t k = 0; k < AOV_PLANES; ++k)
         if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-    return PTRS_OK;
+    return require_device();
 }
 
 int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, uint32_t planes, const DAovFilm &films, float *samples_dev, hipStream_t stream, PtrsStats *stats) {
-    HIPCHK(hipSetDevice(ps->device));
-    HipBackend be;
-    be.ps = ps; be.stream = stream; be.opt = scene_options(ps); be.film_w = prm->width;
-    int rc = get_sobol(ps->device, &be.sob);
-    if (rc != PTRS_OK) return rc;
-    std::string err;
-    rc = render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err);
-    if (rc != PTRS_OK) { if (!err.empty()) g_err = err; return rc; }
-    if (be.rc != PTRS_OK) { if (g_err.empty()) g_err = "device error during render"; return be.rc; }
-    return PTRS_OK;
+    return with_backend(ps, prm, stream, [&](HipBackend &be, std::string &err) { return render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err); });
 }
 
 // The error of a device film against its half film: tile records into tiles_dev, the summary through sum_dev into host memory; on
@@ -2182,25 +2255,17 @@ int do_film_error(int32_t W, int32_t H, const v4 *film, const v4 *half, PtrsTile
     HIPCHK(hipStreamSynchronize(stream));
     return PTRS_OK;
 }
-int cv_select_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
-    HIPCHK(hipSetDevice(device));
-    return PTRS_OK;
-}
 // ptrs_render_range / ptrs_render_range_device / ptrs_render_converged: the checks that need no device, then that there is one
-int range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *film, const void *half) {
+int range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *film, const void *half, RowBand *band_out = nullptr) {
     if (!scene || !camera || !params || !film) { g_err = "null argument"; return PTRS_ERR_INVALID; }
     if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
     if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
     if (half && half == film) { g_err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
-    int32_t rb = params->row_begin, re = params->row_end;
-    if (re <= rb) { rb = 0; re = params->height; }
-    if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-    return PTRS_OK;
+    RowBand band;
+    int rc = row_band(*params, band);
+    if (rc != PTRS_OK) return rc;
+    if (band_out) *band_out = band;
+    return require_device();
 }
 
 // ptrs_denoise / ptrs_denoise_device: the checks that need no device
@@ -2211,14 +2276,6 @@ int dn_check_args(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beaut
     if (out == beauty || out == planes[0] || out == planes[1] || out == planes[2]) { g_err = "out must not be one of the inputs"; return PTRS_ERR_INVALID; }
     return PTRS_OK;
 }
-int dn_select_device(PtrsDenoiser *d) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-    if (d->device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
-    HIPCHK(hipSetDevice(d->device));
-    return PTRS_OK;
-}
-
 template <int S> void dn_launch_lds(const DnIter &it, const v4 *xin, const v4 *gin, v4 *xout, hipStream_t stream) {
     const uint32_t lattice_rows = ((uint32_t)it.H + (uint32_t)S - 1u) / (uint32_t)S; // of residue 0, the longest
     hipLaunchKernelGGL((k_dn_iter_lds<S>), dim3(((uint32_t)it.W + DN_TILE_W - 1u) / DN_TILE_W, (lattice_rows + DN_TILE_T - 1u) / DN_TILE_T, (uint32_t)S), dim3(BLOCK), 0, stream, it, xin, gin, xout);
@@ -2327,25 +2384,20 @@ int ptrs_get_option(const char *name, int64_t *value) {
     return PTRS_ERR_INVALID;
 }
 
-static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out);
-int ptrs_scene_create(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out) { return guarded([&]() { return scene_create_impl(desc, device, out); }); }
 static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out) {
     if (!desc || !out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
-    HIPCHK(hipSetDevice(device));
-    PtrsScene *ps = new PtrsScene();
+    int rc = select_device(device);
+    if (rc != PTRS_OK) return rc;
+    std::unique_ptr<PtrsScene> ps(new PtrsScene());
     ps->device = device;
     const Options opt = options();
-    int rc = build_host_scene(*desc, ps->H, g_err, opt.node_form, opt.node_order);
-    if (rc != PTRS_OK) { delete ps; return rc; }
+    if ((rc = build_host_scene(*desc, ps->H, g_err, opt.node_form, opt.node_order)) != PTRS_OK) return rc;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ps->n_cu = prop.multiProcessorCount;
     HostScene &H = ps->H;
     if ((rc = upload(ps->nodes2, H.nodes2)) || (rc = upload(ps->nodes4, H.nodes4)) || (rc = upload(ps->nodes, H.nodes)) || (rc = upload(ps->tris, H.tris)) || (rc = upload(ps->shade, H.shade)) || (rc = upload(ps->mats, H.mats)) ||
         (rc = upload(ps->texs, H.texs)) || (rc = upload(ps->levels, H.levels)) || (rc = upload(ps->texdata, H.texdata)) || (rc = upload(ps->lights, H.lights)) ||
-        (rc = upload(ps->distdata, H.distdata)) || (rc = upload(ps->inf, H.inf_lights))) { delete ps; return rc; }
+        (rc = upload(ps->distdata, H.distdata)) || (rc = upload(ps->inf, H.inf_lights))) return rc;
     DScene &sc = ps->sc;
     sc.nodes2 = (const DNode2 *)ps->nodes2.p; sc.n_nodes2 = (uint32_t)H.nodes2.size(); sc.nodes4 = (const DNode4 *)ps->nodes4.p; sc.n_nodes4 = (uint32_t)H.nodes4.size();
     sc.nodes = (const DNode *)ps->nodes.p; sc.tris = (const DTri *)ps->tris.p; sc.shade = (const DTriShade *)ps->shade.p; sc.mats = (const DMaterial *)ps->mats.p;
@@ -2361,12 +2413,13 @@ static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScen
     if (H.stack_bound > ps->stack_lds) {
         const size_t threads = (size_t)ps->n_cu * 8 * BLOCK; // no launch holds more than 8 workgroups per CU
         ps->spill_lane_elems = threads * (size_t)(H.stack_bound - ps->stack_lds);
-        if ((rc = ps->stack_spill.ensure(ps->spill_lane_elems * sizeof(unsigned long long))) != PTRS_OK) { delete ps; return rc; } // one lane's worth (ptrs_trace_rays / ptrs_trace_bench); a render grows it to its lanes (HipBackend::begin)
+        if ((rc = ps->stack_spill.ensure(ps->spill_lane_elems * sizeof(unsigned long long))) != PTRS_OK) return rc; // one lane's worth (ptrs_trace_rays / ptrs_trace_bench); a render grows it to its lanes (HipBackend::begin)
         ps->spill.p = (unsigned long long *)ps->stack_spill.p; ps->spill.stride = (uint32_t)threads;
     }
-    *out = ps;
+    *out = ps.release();
     return PTRS_OK;
 }
+int ptrs_scene_create(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out) { return guarded([&]() { return scene_create_impl(desc, device, out); }); }
 
 void ptrs_scene_destroy(PtrsScene *scene) {
     if (!scene) return;
@@ -2383,40 +2436,48 @@ int ptrs_scene_info(PtrsScene *scene, uint64_t *n_nodes, uint64_t *max_depth, ui
 }
 
 int ptrs_render_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, void *film_inout_device, void *hip_stream, PtrsStats *stats) {
-    return guarded([&]() { return do_render(scene, camera, params, (v4 *)film_inout_device, nullptr, (hipStream_t)hip_stream, stats); });
+    return guarded([&]() {
+        HipJob job;
+        job.film = (v4 *)film_inout_device; job.stream = (hipStream_t)hip_stream; job.stats = stats;
+        return do_render(scene, camera, params, job);
+    });
 }
 
-static int render_samples_impl(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats);
-int ptrs_render_samples(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats) {
-    return guarded([&]() { return render_samples_impl(scene, camera, params, film_inout, sample_rgb, stats); });
+// The host-film form of a render, behind the entry point's checks: the band of the film (and of the half film) travels to the scene's device
+// copies, `job` (what the entry point asks for besides films and sample export) runs, the band travels back.  The sample export starts from
+// zeros; with a sample range it starts from the caller's buffer, so that the entries outside the range keep what they held.
+static int render_host_films(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, const RowBand &band, HipJob job,
+                             PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb) {
+    int rc = stage_in(scene->film_tmp, *params, band, film_inout);
+    if (rc != PTRS_OK) return rc;
+    if (film_half_inout && (rc = stage_in(scene->half_tmp, *params, band, film_half_inout)) != PTRS_OK) return rc;
+    const size_t sbytes = sample_rgb ? sample_buffer_bytes(*params, 3) : 0;
+    if (sample_rgb) {
+        if ((rc = scene->samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
+        if (job.sample_range) HIPCHK(hipMemcpy(scene->samples_tmp.p, sample_rgb, sbytes, hipMemcpyHostToDevice));
+        else HIPCHK(hipMemset(scene->samples_tmp.p, 0, sbytes));
+    }
+    job.film = (v4 *)scene->film_tmp.p; job.film_half = film_half_inout ? (v4 *)scene->half_tmp.p : nullptr; job.samples_out = sample_rgb ? (float *)scene->samples_tmp.p : nullptr;
+    rc = do_render(scene, camera, params, job);
+    if (rc != PTRS_OK) return rc;
+    if ((rc = stage_out(scene->film_tmp, band, film_inout)) != PTRS_OK) return rc;
+    if (film_half_inout && (rc = stage_out(scene->half_tmp, band, film_half_inout)) != PTRS_OK) return rc;
+    if (sample_rgb) HIPCHK(hipMemcpy(sample_rgb, scene->samples_tmp.p, sbytes, hipMemcpyDeviceToHost));
+    return PTRS_OK;
 }
 static int render_samples_impl(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats) {
     if (!scene || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
     HIPCHK(hipSetDevice(scene->device));
-    const size_t npx = (size_t)params->width * (size_t)params->height;
-    int rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel));
+    int rc = scene->film_tmp.ensure((size_t)params->width * (size_t)params->height * sizeof(PtrsFilmPixel));
     if (rc != PTRS_OK) return rc;
-    // only the rows of the band travel (rows outside [row_begin, row_end) are untouched: concurrent renders of disjoint
-    // bands into one host film, one per device, do not step on each other)
-    int32_t rb = params->row_begin, re = params->row_end;
-    if (re <= rb) { rb = 0; re = params->height; }
-    if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
-    const size_t band_off = (size_t)rb * (size_t)params->width, band_px = (size_t)(re - rb) * (size_t)params->width;
-    HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->film_tmp.p + band_off, film_inout + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyHostToDevice));
-    float *sdev = nullptr; size_t sbytes = 0;
-    if (sample_rgb) {
-        const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
-        const size_t spp = params->sampler == PTRS_SAMPLER_STRATIFIED ? (size_t)std::max(params->spp, 1) : (size_t)g.spp; // the stratified sampler takes spp = dim^2 as is
-        sbytes = (size_t)g.NX * (size_t)g.NY * spp * 3 * sizeof(float);
-        if ((rc = scene->samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
-        HIPCHK(hipMemset(scene->samples_tmp.p, 0, sbytes));
-        sdev = (float *)scene->samples_tmp.p;
-    }
-    rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, sdev, nullptr, stats);
-    if (rc != PTRS_OK) return rc;
-    HIPCHK(hipMemcpy(film_inout + band_off, (PtrsFilmPixel *)scene->film_tmp.p + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
-    if (sample_rgb) HIPCHK(hipMemcpy(sample_rgb, sdev, sbytes, hipMemcpyDeviceToHost));
-    return PTRS_OK;
+    RowBand band;
+    if ((rc = row_band(*params, band)) != PTRS_OK) return rc;
+    HipJob job;
+    job.stats = stats;
+    return render_host_films(scene, camera, params, band, job, film_inout, nullptr, sample_rgb);
+}
+int ptrs_render_samples(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats) {
+    return guarded([&]() { return render_samples_impl(scene, camera, params, film_inout, sample_rgb, stats); });
 }
 
 int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES],
@@ -2437,34 +2498,25 @@ int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRender
         if (rc != PTRS_OK) return rc;
         if (params->width <= 0 || params->height <= 0 || params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
         HIPCHK(hipSetDevice(scene->device));
-        // only the rows of the band travel, like ptrs_render_samples
-        int32_t rb = params->row_begin, re = params->row_end;
-        if (re <= rb) { rb = 0; re = params->height; }
-        if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
-        const size_t npx = (size_t)params->width * (size_t)params->height;
-        const size_t band_off = (size_t)rb * (size_t)params->width, band_px = (size_t)(re - rb) * (size_t)params->width;
+        RowBand band;
+        if ((rc = row_band(*params, band)) != PTRS_OK) return rc;
         DAovFilm F;
         for (uint32_t k = 0; k < AOV_PLANES; ++k) {
             F.plane[k] = nullptr;
             if (!(planes & (1u << k))) continue;
-            if ((rc = scene->aov_film_tmp[k].ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
+            if ((rc = stage_in(scene->aov_film_tmp[k], *params, band, planes_inout[k])) != PTRS_OK) return rc;
             F.plane[k] = (v4 *)scene->aov_film_tmp[k].p;
-            HIPCHK(hipMemcpy((PtrsFilmPixel *)F.plane[k] + band_off, planes_inout[k] + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyHostToDevice));
         }
-        float *sdev = nullptr; size_t sbytes = 0;
+        const size_t sbytes = sample_aov ? sample_buffer_bytes(*params, PTRS_AOV_SAMPLE_FLOATS) : 0;
         if (sample_aov) {
-            const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
-            const size_t spp = params->sampler == PTRS_SAMPLER_STRATIFIED ? (size_t)std::max(params->spp, 1) : (size_t)g.spp;
-            sbytes = (size_t)g.NX * (size_t)g.NY * spp * PTRS_AOV_SAMPLE_FLOATS * sizeof(float);
             if ((rc = scene->aov_samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
             HIPCHK(hipMemset(scene->aov_samples_tmp.p, 0, sbytes));
-            sdev = (float *)scene->aov_samples_tmp.p;
         }
-        rc = do_render_aov(scene, camera, params, planes, F, sdev, nullptr, stats);
+        rc = do_render_aov(scene, camera, params, planes, F, sample_aov ? (float *)scene->aov_samples_tmp.p : nullptr, nullptr, stats);
         if (rc != PTRS_OK) return rc;
         for (uint32_t k = 0; k < AOV_PLANES; ++k)
-            if (F.plane[k]) HIPCHK(hipMemcpy(planes_inout[k] + band_off, (PtrsFilmPixel *)F.plane[k] + band_off, band_px * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
-        if (sample_aov) HIPCHK(hipMemcpy(sample_aov, sdev, sbytes, hipMemcpyDeviceToHost));
+            if (F.plane[k] && (rc = stage_out(scene->aov_film_tmp[k], band, planes_inout[k])) != PTRS_OK) return rc;
+        if (sample_aov) HIPCHK(hipMemcpy(sample_aov, scene->aov_samples_tmp.p, sbytes, hipMemcpyDeviceToHost));
         return PTRS_OK;
     });
 }
@@ -2495,7 +2547,7 @@ void ptrs_denoiser_destroy(PtrsDenoiser *d) {
 int ptrs_denoise_device(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty_device, const void *const planes_device[PTRS_AOV_PLANES], void *out_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
         int rc = dn_check_args(d, p, beauty_device, planes_device, out_device);
-        if (rc != PTRS_OK || (rc = dn_select_device(d)) != PTRS_OK) return rc;
+        if (rc != PTRS_OK || (rc = select_device(d->device)) != PTRS_OK) return rc;
         const v4 *planes[AOV_PLANES] = {(const v4 *)planes_device[0], (const v4 *)planes_device[1], (const v4 *)planes_device[2]};
         return do_denoise(d, p, (const v4 *)beauty_device, planes, (v4 *)out_device, (hipStream_t)hip_stream, stats, 0);
     });
@@ -2504,7 +2556,7 @@ int ptrs_denoise_device(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void 
 int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixel *beauty, const PtrsFilmPixel *const planes[PTRS_AOV_PLANES], PtrsFilmPixel *out, PtrsStats *stats) {
     return guarded([&]() -> int {
         int rc = dn_check_args(d, p, beauty, (const void *const *)planes, out);
-        if (rc != PTRS_OK || (rc = dn_select_device(d)) != PTRS_OK) return rc;
+        if (rc != PTRS_OK || (rc = select_device(d->device)) != PTRS_OK) return rc;
         const auto t_begin = std::chrono::steady_clock::now();
         const size_t bytes = (size_t)d->W * (size_t)d->H * sizeof(PtrsFilmPixel);
         const PtrsFilmPixel *src[4] = {beauty, planes[0], planes[1], planes[2]};
@@ -2525,42 +2577,23 @@ int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const P
         int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout_device, film_half_inout_device);
         if (rc != PTRS_OK) return rc;
         const uint32_t range[2] = {sample_begin, sample_end};
-        return do_render(scene, camera, params, (v4 *)film_inout_device, nullptr, (hipStream_t)hip_stream, stats, nullptr, nullptr, nullptr, 1, nullptr, nullptr, range, (v4 *)film_half_inout_device);
+        HipJob job;
+        job.film = (v4 *)film_inout_device; job.film_half = (v4 *)film_half_inout_device; job.sample_range = range; job.stream = (hipStream_t)hip_stream; job.stats = stats;
+        return do_render(scene, camera, params, job);
     });
 }
 
 int ptrs_render_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
                       PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout, film_half_inout);
+        RowBand band;
+        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout, film_half_inout, &band);
         if (rc != PTRS_OK) return rc;
         HIPCHK(hipSetDevice(scene->device));
-        // only the rows of the band travel, like ptrs_render_samples
-        int32_t rb = params->row_begin, re = params->row_end;
-        if (re <= rb) { rb = 0; re = params->height; }
-        const size_t npx = (size_t)params->width * (size_t)params->height;
-        const size_t band_off = (size_t)rb * (size_t)params->width, band_bytes = (size_t)(re - rb) * (size_t)params->width * sizeof(PtrsFilmPixel);
-        if ((rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->film_tmp.p + band_off, film_inout + band_off, band_bytes, hipMemcpyHostToDevice));
-        if (film_half_inout) {
-            if ((rc = scene->half_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
-            HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->half_tmp.p + band_off, film_half_inout + band_off, band_bytes, hipMemcpyHostToDevice));
-        }
-        float *sdev = nullptr; size_t sbytes = 0;
-        if (sample_rgb) { // the caller's buffer travels there and back: the entries outside the range keep what they held
-            const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
-            sbytes = (size_t)g.NX * (size_t)g.NY * (size_t)total_spp(*params) * 3 * sizeof(float);
-            if ((rc = scene->samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
-            HIPCHK(hipMemcpy(scene->samples_tmp.p, sample_rgb, sbytes, hipMemcpyHostToDevice));
-            sdev = (float *)scene->samples_tmp.p;
-        }
         const uint32_t range[2] = {sample_begin, sample_end};
-        rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, sdev, nullptr, stats, nullptr, nullptr, nullptr, 1, nullptr, nullptr, range, film_half_inout ? (v4 *)scene->half_tmp.p : nullptr);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy(film_inout + band_off, (PtrsFilmPixel *)scene->film_tmp.p + band_off, band_bytes, hipMemcpyDeviceToHost));
-        if (film_half_inout) HIPCHK(hipMemcpy(film_half_inout + band_off, (PtrsFilmPixel *)scene->half_tmp.p + band_off, band_bytes, hipMemcpyDeviceToHost));
-        if (sample_rgb) HIPCHK(hipMemcpy(sample_rgb, sdev, sbytes, hipMemcpyDeviceToHost));
-        return PTRS_OK;
+        HipJob job;
+        job.sample_range = range; job.stats = stats;
+        return render_host_films(scene, camera, params, band, job, film_inout, film_half_inout, sample_rgb);
     });
 }
 
@@ -2568,13 +2601,12 @@ int ptrs_film_error_device(int32_t device, int32_t width, int32_t height, const 
     return guarded([&]() -> int {
         if (const char *m = cv_check_args(width, height, film_device, half_device, summary_out)) { g_err = m; return PTRS_ERR_INVALID; }
         if (!tiles_out_device) { g_err = "null argument (the device form needs tiles_out_device)"; return PTRS_ERR_INVALID; }
-        int rc = cv_select_device(device);
+        int rc = select_device(device);
         if (rc != PTRS_OK) return rc;
         DevBuf sum; // (a handle-free call owns nothing between calls: 24 bytes for the summary's way to the host)
         if ((rc = sum.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
         rc = do_film_error(width, height, (const v4 *)film_device, (const v4 *)half_device, (PtrsTileError *)tiles_out_device, (PtrsFilmErrorSummary *)sum.p, (hipStream_t)hip_stream, summary_out);
-        if (rc != PTRS_OK) (void)hipStreamSynchronize((hipStream_t)hip_stream);
-        sum.release();
+        if (rc != PTRS_OK) (void)hipStreamSynchronize((hipStream_t)hip_stream); // (nothing of the call is in flight when `sum` goes)
         return rc;
     });
 }
@@ -2582,24 +2614,17 @@ int ptrs_film_error_device(int32_t device, int32_t width, int32_t height, const 
 int ptrs_film_error(int32_t device, int32_t width, int32_t height, const PtrsFilmPixel *film, const PtrsFilmPixel *half, PtrsTileError *tiles_out, PtrsFilmErrorSummary *summary_out) {
     return guarded([&]() -> int {
         if (const char *m = cv_check_args(width, height, film, half, summary_out)) { g_err = m; return PTRS_ERR_INVALID; }
-        int rc = cv_select_device(device);
+        int rc = select_device(device);
         if (rc != PTRS_OK) return rc;
         const size_t bytes = (size_t)width * (size_t)height * sizeof(PtrsFilmPixel);
         const size_t n_tiles = (size_t)(((uint32_t)width + CV_TILE - 1u) / CV_TILE) * (size_t)(((uint32_t)height + CV_TILE - 1u) / CV_TILE);
-        DevBuf f, h, t, sum;
-        auto work = [&]() -> int {
-            int r;
-            if ((r = f.ensure(bytes)) != PTRS_OK || (r = h.ensure(bytes)) != PTRS_OK || (r = t.ensure(n_tiles * sizeof(PtrsTileError))) != PTRS_OK || (r = sum.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return r;
-            HIPCHK(hipMemcpy(f.p, film, bytes, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(h.p, half, bytes, hipMemcpyHostToDevice));
-            if ((r = do_film_error(width, height, (const v4 *)f.p, (const v4 *)h.p, (PtrsTileError *)t.p, (PtrsFilmErrorSummary *)sum.p, nullptr, summary_out)) != PTRS_OK) return r;
-            if (tiles_out) HIPCHK(hipMemcpy(tiles_out, t.p, n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost));
-            return PTRS_OK;
-        };
-        rc = work();
-        if (rc != PTRS_OK) (void)hipDeviceSynchronize();
-        f.release(); h.release(); t.release(); sum.release();
-        return rc;
+        DevBuf f, h, t, sum; // (freed on every return; hipFree waits for what is in flight)
+        if ((rc = f.ensure(bytes)) != PTRS_OK || (rc = h.ensure(bytes)) != PTRS_OK || (rc = t.ensure(n_tiles * sizeof(PtrsTileError))) != PTRS_OK || (rc = sum.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(f.p, film, bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h.p, half, bytes, hipMemcpyHostToDevice));
+        if ((rc = do_film_error(width, height, (const v4 *)f.p, (const v4 *)h.p, (PtrsTileError *)t.p, (PtrsFilmErrorSummary *)sum.p, nullptr, summary_out)) != PTRS_OK) return rc;
+        if (tiles_out) HIPCHK(hipMemcpy(tiles_out, t.p, n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost));
+        return PTRS_OK;
     });
 }
 
@@ -2636,7 +2661,9 @@ int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
             const uint32_t parts[2][2] = {{blocks[3 * k], blocks[3 * k + 1]}, {blocks[3 * k + 1], blocks[3 * k + 2]}};
             for (int h = 0; h < 2; ++h) { // the block's first half into both films, its second half into the film only
                 PtrsStats st;
-                if ((rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, nullptr, nullptr, &st, nullptr, nullptr, nullptr, 1, nullptr, nullptr, parts[h], h == 0 ? (v4 *)scene->half_tmp.p : nullptr)) != PTRS_OK) return rc;
+                HipJob job;
+                job.film = (v4 *)scene->film_tmp.p; job.film_half = h == 0 ? (v4 *)scene->half_tmp.p : nullptr; job.sample_range = parts[h]; job.stats = &st;
+                if ((rc = do_render(scene, camera, params, job)) != PTRS_OK) return rc;
                 total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
                 total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
                 total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
@@ -2667,19 +2694,13 @@ int ptrs_render_progressive(PtrsScene *scene, const PtrsCamera *camera, const Pt
     return guarded([&]() -> int {
         if (!scene || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         HIPCHK(hipSetDevice(scene->device));
-        int32_t rb = params->row_begin, re = params->row_end;
-        if (re <= rb) { rb = 0; re = params->height; }
-        if (rb < 0 || re > params->height) { g_err = "row band outside the film"; return PTRS_ERR_INVALID; }
-        const size_t npx = (size_t)params->width * (size_t)params->height;
-        int rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel));
+        RowBand band;
+        int rc = row_band(*params, band);
         if (rc != PTRS_OK) return rc;
-        const size_t off = (size_t)rb * (size_t)params->width, cnt = (size_t)(re - rb) * (size_t)params->width;
-        HIPCHK(hipMemcpy((PtrsFilmPixel *)scene->film_tmp.p + off, film_inout + off, cnt * sizeof(PtrsFilmPixel), hipMemcpyHostToDevice));
         const RenderProgress pg{fn, user};
-        rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, nullptr, nullptr, stats, nullptr, &pg, film_inout);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy(film_inout + off, (PtrsFilmPixel *)scene->film_tmp.p + off, cnt * sizeof(PtrsFilmPixel), hipMemcpyDeviceToHost));
-        return PTRS_OK;
+        HipJob job;
+        job.progress = &pg; job.host_film = film_inout; job.stats = stats;
+        return render_host_films(scene, camera, params, band, job, film_inout, nullptr, nullptr);
     });
 }
 
@@ -2704,7 +2725,9 @@ int ptrs_render_row_cost(PtrsScene *scene, const PtrsCamera *camera, const PtrsR
         HIPCHK(hipMemset(scene->row_cost.p, 0, (size_t)g.NY * 4));
         PtrsRenderParams p = *params;
         p.row_begin = 0; p.row_end = p.height;
-        rc = do_render(scene, camera, &p, nullptr, nullptr, nullptr, stats, nullptr, nullptr, nullptr, 1, nullptr, (uint32_t *)scene->row_cost.p);
+        HipJob job;
+        job.row_cost = (uint32_t *)scene->row_cost.p; job.stats = stats;
+        rc = do_render(scene, camera, &p, job);
         if (rc != PTRS_OK) return rc;
         std::vector<uint32_t> h((size_t)g.NY);
         HIPCHK(hipMemcpy(h.data(), scene->row_cost.p, (size_t)g.NY * 4, hipMemcpyDeviceToHost));
@@ -2767,7 +2790,9 @@ int ptrs_render_multi(PtrsScene *const *scenes, uint32_t n, const PtrsCamera *ca
                 if (film_is_zero) HIPCHK(hipMemset(band, 0, bytes)); else HIPCHK(hipMemcpy(band, film_inout + off, bytes, hipMemcpyHostToDevice));
                 PtrsRenderParams p = *params;
                 p.row_begin = bounds[i]; p.row_end = bounds[i + 1]; p.device = ps->device;
-                int rc2 = do_render(ps, camera, &p, (v4 *)(band - off), nullptr, nullptr, stats_per_scene ? &stats_per_scene[i] : nullptr, nullptr, nullptr, nullptr, std::max(1, share[i]));
+                HipJob job;
+                job.film = (v4 *)(band - off); job.stats = stats_per_scene ? &stats_per_scene[i] : nullptr; job.share = std::max(1, share[i]);
+                int rc2 = do_render(ps, camera, &p, job);
                 if (rc2 != PTRS_OK || ps == root) return rc2;
                 PtrsFilmPixel *dst = (PtrsFilmPixel *)root->film_tmp.p + off;
                 const bool direct = scene_options(ps).peer_copy != 0; // (0: the test hook that forces the host-staged path, also between replicas on one device)
@@ -2823,70 +2848,65 @@ int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera, const P
         if (rc != PTRS_OK) return rc;
         HIPCHK(hipMemset(scene->samples_tmp.p, 0, bytes));
         const int32_t pixel[2] = {px, py};
-        rc = do_render(scene, camera, params, nullptr, (float *)scene->samples_tmp.p, nullptr, nullptr, pixel);
+        HipJob job;
+        job.samples_out = (float *)scene->samples_tmp.p; job.single_pixel = pixel;
+        rc = do_render(scene, camera, params, job);
         if (rc != PTRS_OK) return rc;
         HIPCHK(hipMemcpy(rgb_out, scene->samples_tmp.p, bytes, hipMemcpyDeviceToHost));
         return PTRS_OK;
     });
 }
 
-static int trace_rays_impl(PtrsScene *scene, uint32_t n, const float *rays, int32_t any_hit, PtrsHit *hits_out, PtrsStats *stats);
-int ptrs_trace_rays(PtrsScene *scene, uint32_t n, const float *rays, int32_t any_hit, PtrsHit *hits_out, PtrsStats *stats) {
-    return guarded([&]() { return trace_rays_impl(scene, n, rays, any_hit, hits_out, stats); });
-}
 static int trace_rays_impl(PtrsScene *scene, uint32_t n, const float *rays, int32_t any_hit, PtrsHit *hits_out, PtrsStats *stats) {
     if (!scene || (n && (!rays || !hits_out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
     if (scene->H.max_depth > 64) { g_err = "BVH deeper than 64"; return PTRS_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(scene->device));
+    int rc = require_spill(scene);
+    if (rc != PTRS_OK) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return PTRS_OK;
     std::vector<v4> ro(n), rd(n);
     for (uint32_t i = 0; i < n; ++i) { ro[i].x = rays[7 * i]; ro[i].y = rays[7 * i + 1]; ro[i].z = rays[7 * i + 2]; ro[i].w = rays[7 * i + 6]; rd[i].x = rays[7 * i + 3]; rd[i].y = rays[7 * i + 4]; rd[i].z = rays[7 * i + 5]; rd[i].w = 0.0f; }
     DevBuf bo, bd, bh, bc, bs, bt;
-    int rc;
-    if ((rc = upload(bo, ro)) || (rc = upload(bd, rd)) || (rc = bh.ensure((size_t)n * 16)) || (rc = bc.ensure(16)) || (rc = bs.ensure(CNT_NUM * 8)) || (rc = bt.ensure((size_t)n * 4))) { bo.release(); bd.release(); bh.release(); bc.release(); bs.release(); bt.release(); return rc; }
-    hipError_t e = hipMemcpy(bc.p, &n, 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(bs.p, 0, CNT_NUM * 8);
+    if ((rc = upload(bo, ro)) || (rc = upload(bd, rd)) || (rc = bh.ensure((size_t)n * 16)) || (rc = bc.ensure(16)) || (rc = bs.ensure(CNT_NUM * 8)) || (rc = bt.ensure((size_t)n * 4))) return rc;
+    HIPCHK(hipMemcpy(bc.p, &n, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(bs.p, 0, CNT_NUM * 8));
     const uint32_t gmax = (uint32_t)scene->n_cu * 8u; // the spill columns are sized for this many workgroups
     dim3 g((n + BLOCK - 1) / BLOCK > gmax ? gmax : (n + BLOCK - 1) / BLOCK), b(BLOCK);
     hipEvent_t ea, eb; (void)hipEventCreate(&ea); (void)hipEventCreate(&eb);
     (void)hipEventRecord(ea, nullptr);
-#define LAUNCH_T(ANYV)                                                                                                                                  \
-    do {                                                                                                                                                \
-        const StackSpill sp = scene->spill;                                                                                                             \
-        if (scene->stack_lds == 8 && !sp.p) hipLaunchKernelGGL((k_trace<ANYV, 8, false>), g, b, 0, nullptr, scene->sc, sp, (const uint32_t *)nullptr, (const uint32_t *)bc.p, (const v4 *)bo.p, (const v4 *)bd.p, (u4 *)bh.p, (uint32_t *)bh.p, (float *)bt.p, (unsigned long long *)bs.p, 1u); \
-        else if (scene->stack_lds == 8) hipLaunchKernelGGL((k_trace<ANYV, 8, true>), g, b, 0, nullptr, scene->sc, sp, (const uint32_t *)nullptr, (const uint32_t *)bc.p, (const v4 *)bo.p, (const v4 *)bd.p, (u4 *)bh.p, (uint32_t *)bh.p, (float *)bt.p, (unsigned long long *)bs.p, 1u); \
-        else if (!sp.p) hipLaunchKernelGGL((k_trace<ANYV, 16, false>), g, b, 0, nullptr, scene->sc, sp, (const uint32_t *)nullptr, (const uint32_t *)bc.p, (const v4 *)bo.p, (const v4 *)bd.p, (u4 *)bh.p, (uint32_t *)bh.p, (float *)bt.p, (unsigned long long *)bs.p, 1u); \
-        else hipLaunchKernelGGL((k_trace<ANYV, 16, true>), g, b, 0, nullptr, scene->sc, sp, (const uint32_t *)nullptr, (const uint32_t *)bc.p, (const v4 *)bo.p, (const v4 *)bd.p, (u4 *)bh.p, (uint32_t *)bh.p, (float *)bt.p, (unsigned long long *)bs.p, 1u); \
-    } while (0)
-    if (any_hit) LAUNCH_T(true); else LAUNCH_T(false);
-#undef LAUNCH_T
+    typedef void (*TraceFn)(DScene, StackSpill, const uint32_t *, const uint32_t *, const v4 *, const v4 *, u4 *, uint32_t *, float *, unsigned long long *, uint32_t);
+    const StackSpill sp = scene->spill;
+#define PICK_T(ANYV) (scene->stack_lds == 8 ? (!sp.p ? (TraceFn)k_trace<ANYV, 8, false> : (TraceFn)k_trace<ANYV, 8, true>) : (!sp.p ? (TraceFn)k_trace<ANYV, 16, false> : (TraceFn)k_trace<ANYV, 16, true>))
+    const TraceFn fn = any_hit ? PICK_T(true) : PICK_T(false);
+#undef PICK_T
+    hipLaunchKernelGGL(fn, g, b, 0, nullptr, scene->sc, sp, (const uint32_t *)nullptr, (const uint32_t *)bc.p, (const v4 *)bo.p, (const v4 *)bd.p, (u4 *)bh.p, (uint32_t *)bh.p, (float *)bt.p, (unsigned long long *)bs.p, 1u);
     (void)hipEventRecord(eb, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     float ms = 0.0f; (void)hipEventElapsedTime(&ms, ea, eb);
     (void)hipEventDestroy(ea); (void)hipEventDestroy(eb);
-    if (e == hipSuccess) {
-        if (any_hit) {
-            std::vector<uint32_t> oc(n);
-            e = hipMemcpy(oc.data(), bh.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-            for (uint32_t i = 0; i < n; ++i) { hits_out[i].prim = oc[i] ? 0 : -1; hits_out[i].t = rays[7 * i + 6]; hits_out[i].b0 = hits_out[i].b1 = hits_out[i].b2 = 0.0f; }
-        } else {
-            std::vector<u4> hh(n); std::vector<float> tt(n);
-            e = hipMemcpy(hh.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(tt.data(), bt.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-            for (uint32_t i = 0; i < n; ++i) { hits_out[i].prim = (int32_t)hh[i].x; hits_out[i].b0 = u2f(hh[i].y); hits_out[i].b1 = u2f(hh[i].z); hits_out[i].b2 = u2f(hh[i].w); hits_out[i].t = tt[i]; }
-        }
+    if (e != hipSuccess) { g_err = std::string("ptrs_trace_rays: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+    if (any_hit) {
+        std::vector<uint32_t> oc(n);
+        HIPCHK(hipMemcpy(oc.data(), bh.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) { hits_out[i].prim = oc[i] ? 0 : -1; hits_out[i].t = rays[7 * i + 6]; hits_out[i].b0 = hits_out[i].b1 = hits_out[i].b2 = 0.0f; }
+    } else {
+        std::vector<u4> hh(n); std::vector<float> tt(n);
+        HIPCHK(hipMemcpy(hh.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(tt.data(), bt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) { hits_out[i].prim = (int32_t)hh[i].x; hits_out[i].b0 = u2f(hh[i].y); hits_out[i].b1 = u2f(hh[i].z); hits_out[i].b2 = u2f(hh[i].w); hits_out[i].t = tt[i]; }
     }
-    if (e == hipSuccess && stats) {
+    if (stats) {
         unsigned long long hs[CNT_NUM];
-        e = hipMemcpy(hs, bs.p, sizeof(hs), hipMemcpyDeviceToHost);
+        HIPCHK(hipMemcpy(hs, bs.p, sizeof(hs), hipMemcpyDeviceToHost));
         stats->nodes_visited = hs[CNT_NODES]; stats->tris_tested = hs[CNT_TRIS]; stats->ms_trace = ms; stats->trace_launches = 1; stats->kernel_launches = 1;
         if (any_hit) stats->rays_shadow = n; else stats->rays_extension = n;
     }
-    bo.release(); bd.release(); bh.release(); bc.release(); bs.release(); bt.release();
-    if (e != hipSuccess) { g_err = std::string("ptrs_trace_rays: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
     return PTRS_OK;
+}
+int ptrs_trace_rays(PtrsScene *scene, uint32_t n, const float *rays, int32_t any_hit, PtrsHit *hits_out, PtrsStats *stats) {
+    return guarded([&]() { return trace_rays_impl(scene, n, rays, any_hit, hits_out, stats); });
 }
 
 int ptrs_render_dump_rays(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t round, uint32_t max_rays, float *rays_out, uint32_t *n_out) {
@@ -2897,15 +2917,19 @@ int ptrs_render_dump_rays(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
         int rc = out.ensure((size_t)max_rays * 7 * sizeof(float));
         if (rc != PTRS_OK) return rc;
         const size_t npx = (size_t)params->width * (size_t)params->height;
-        if ((rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) { out.release(); return rc; }
+        if ((rc = scene->film_tmp.ensure(npx * sizeof(PtrsFilmPixel))) != PTRS_OK) return rc;
         const RayDump d{round, max_rays, (float *)out.p, n_out};
         *n_out = 0;
-        rc = do_render(scene, camera, params, (v4 *)scene->film_tmp.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, &d);
-        if (rc == PTRS_OK && *n_out && hipMemcpy(rays_out, out.p, (size_t)*n_out * 7 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "copying the rays out failed"; rc = PTRS_ERR_DEVICE; }
-        out.release();
-        return rc;
+        HipJob job;
+        job.film = (v4 *)scene->film_tmp.p; job.dump = &d;
+        rc = do_render(scene, camera, params, job);
+        if (rc != PTRS_OK) return rc;
+        if (*n_out && hipMemcpy(rays_out, out.p, (size_t)*n_out * 7 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "copying the rays out failed"; return PTRS_ERR_DEVICE; }
+        return PTRS_OK;
     });
 }
+
+HipBackend::TravFn HipBackend::pick_extend(int ft, bool v, bool ovf) { return ft == FEAT_FULL ? pick_extend_t<FEAT_FULL>(v, ovf) : ft == FEAT_IMG_ENV ? pick_extend_t<FEAT_IMG_ENV>(v, ovf) : pick_extend_t<FEAT_SIMPLE>(v, ovf); } // (here: see epilogue_fn)
 
 // Traversal alone, the way a frame runs it: the rays are uploaded once, laid out as one pass's path state with an extension queue in
 // segments (64-ray blocks dealt round-robin, like k_generate's), and the lane-refill extension kernel of this scene (phase voting,
@@ -2915,13 +2939,12 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         if (!scene || !rays || n == 0 || repeats == 0 || !stats) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         if (scene->H.max_depth > 64) { g_err = "BVH deeper than 64"; return PTRS_ERR_UNSUPPORTED; }
         HIPCHK(hipSetDevice(scene->device));
+        int rc = require_spill(scene);
+        if (rc != PTRS_OK) return rc;
         std::memset(stats, 0, sizeof(*stats));
         HipBackend be;
         be.ps = scene; be.stream = nullptr; be.opt = scene_options(scene); be.sc = scene->sc;
-        be.feat_trace = scene_trace_features(scene->H);
-        be.vote = be.opt.vote >= 0 ? be.opt.vote != 0 : true;
-        be.refill = (uint32_t)(be.opt.refill > 0 ? be.opt.refill : (be.opt.refill == 0 ? 64 : ((be.vote && be.feat_trace == FEAT_SIMPLE) ? 32 : 16)));
-        be.geom4 = be.sc.n_nodes4 ? 0xffffffffu : LN_V4 * be.sc.n_nodes2 + 9u * be.sc.n_prims;
+        be.traversal_policy(scene_trace_features(scene->H));
         const uint32_t chunks = (n + 63u) / 64u, gmax = (uint32_t)scene->n_cu * 8u * (uint32_t)(be.opt.grid_mult ? be.opt.grid_mult : 8); // (one launch at a time: the single-lane segmentation)
         const uint32_t G = chunks < gmax ? chunks : gmax, seg_cap = ((chunks + G - 1) / G) * 64u;
         if ((uint64_t)G * seg_cap * 16ull >= (1ull << 32)) { g_err = "ptrs_trace_bench: too many rays for one launch (queue positions are 32-bit byte offsets of 16-byte records: fewer than 2^28)"; return PTRS_ERR_INVALID; }
@@ -2945,17 +2968,15 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
             cnt[(size_t)Q_EXT * G + s] += m;
         }
         DevBuf bo, bd, bh, bq, bc, bt, bs;
-        auto cleanup = [&]() { bo.release(); bd.release(); bh.release(); bq.release(); bc.release(); bt.release(); bs.release(); };
-        int rc;
         const size_t tk_words = (size_t)(repeats + 1) * TK_LAUNCH_WORDS + 4;
-        if ((rc = upload(bo, ro)) || (rc = upload(bd, rd)) || (rc = bh.ensure(nq * 16)) || (rc = upload(bq, q)) || (rc = upload(bc, cnt)) || (rc = bt.ensure(tk_words * 4)) || (rc = bs.ensure(CNT_NUM * 8))) { cleanup(); return rc; }
+        if ((rc = upload(bo, ro)) || (rc = upload(bd, rd)) || (rc = bh.ensure(nq * 16)) || (rc = upload(bq, q)) || (rc = upload(bc, cnt)) || (rc = bt.ensure(tk_words * 4)) || (rc = bs.ensure(CNT_NUM * 8))) return rc;
         hipError_t e = hipMemset(bt.p, 0, tk_words * 4);
         if (e == hipSuccess) e = hipMemset(bs.p, 0, CNT_NUM * 8);
         DPaths P; std::memset(&P, 0, sizeof(P)); P.ray_o[0] = (v4 *)bo.p; P.ray_d[0] = (v4 *)bd.p; P.hit = (u4 *)bh.p;
         DQueues Q; std::memset(&Q, 0, sizeof(Q)); Q.ext[0] = (uint32_t *)bq.p; Q.counts = (uint32_t *)bc.p; Q.stats = (unsigned long long *)bs.p; Q.tickets = (uint32_t *)bt.p; Q.alive = (uint32_t *)bt.p + (size_t)(repeats + 1) * TK_LAUNCH_WORDS;
         DParams R; std::memset(&R, 0, sizeof(R)); R.n_paths = n;
         StackSpill sp = scene->spill;
-        const HipBackend::TravFn fn = be.feat_trace == FEAT_FULL ? be.pick_extend<FEAT_FULL>(be.vote, sp.p != nullptr) : (be.feat_trace == FEAT_IMG_ENV ? be.pick_extend<FEAT_IMG_ENV>(be.vote, sp.p != nullptr) : be.pick_extend<FEAT_SIMPLE>(be.vote, sp.p != nullptr));
+        const HipBackend::TravFn fn = be.pick_extend(be.feat_trace, be.vote, sp.p != nullptr);
         const uint32_t grid = be.persistent_grid(fn, HipBackend::T_EXTEND);
         std::vector<hipEvent_t> ev(2 * (size_t)repeats, nullptr);
         for (auto &x : ev) if (e == hipSuccess) e = hipEventCreate(&x); // (destroyed below on every path: nothing between here and there returns)
@@ -2970,14 +2991,13 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         double ms = 0.0;
         for (uint32_t k = 0; k < repeats && e == hipSuccess; ++k) { float t = 0.0f; e = hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]); ms += t; }
         for (auto &x : ev) if (x) (void)hipEventDestroy(x);
-        if (e == hipSuccess) {
-            unsigned long long hs[CNT_NUM];
-            e = hipMemcpy(hs, bs.p, sizeof(hs), hipMemcpyDeviceToHost);
-            stats->nodes_visited = hs[CNT_NODES]; stats->tris_tested = hs[CNT_TRIS];
-        }
-        if (e == hipSuccess && hits_out) {
+        if (e != hipSuccess) { g_err = std::string("ptrs_trace_bench: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+        unsigned long long hs[CNT_NUM];
+        HIPCHK(hipMemcpy(hs, bs.p, sizeof(hs), hipMemcpyDeviceToHost));
+        stats->nodes_visited = hs[CNT_NODES]; stats->tris_tested = hs[CNT_TRIS];
+        if (hits_out) {
             std::vector<u4> hh(nq);
-            e = hipMemcpy(hh.data(), bh.p, nq * 16, hipMemcpyDeviceToHost);
+            HIPCHK(hipMemcpy(hh.data(), bh.p, nq * 16, hipMemcpyDeviceToHost));
             for (uint32_t c = 0; c < chunks; ++c) {
                 const uint32_t m = c * 64u + 64u <= n ? 64u : n - c * 64u;
                 for (uint32_t k = 0; k < m; ++k) {
@@ -2989,8 +3009,6 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         stats->ms_trace = ms; stats->ms_extend = ms; stats->trace_launches = repeats; stats->extend_launches = repeats; stats->kernel_launches = repeats + 1; stats->rays_extension = (uint64_t)n * repeats;
         stats->queue_segments = G; stats->grid_wgs[0] = grid; stats->resident_wgs_per_cu[0] = be.last_per_cu[HipBackend::T_EXTEND];
         stats->stack_lds = scene->stack_lds; stats->lds_form_v4 = be.geom4 == 0xffffffffu ? 0u : be.geom4;
-        cleanup();
-        if (e != hipSuccess) { g_err = std::string("ptrs_trace_bench: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
         return PTRS_OK;
     });
 }
@@ -2998,29 +3016,43 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
 int ptrs_selftest_div3(int32_t device, uint32_t mode, uint64_t n_sets, uint64_t seed, uint64_t *mismatches_out, uint64_t *fast_path_sets_out, uint32_t *first_bad_out) {
     return guarded([&]() -> int {
         if (!mismatches_out || mode > 4u || n_sets == 0) { g_err = "bad self-test request"; return PTRS_ERR_INVALID; }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
-        if (device < 0 || device >= ndev) { g_err = "device ordinal out of range"; return PTRS_ERR_INVALID; }
-        HIPCHK(hipSetDevice(device));
+        int rc = select_device(device);
+        if (rc != PTRS_OK) return rc;
         DevBuf out, fb;
-        int rc;
-        if ((rc = out.ensure(16)) != PTRS_OK || (rc = fb.ensure(44)) != PTRS_OK) { out.release(); fb.release(); return rc; }
-        hipError_t e = hipMemset(out.p, 0, 16);
-        if (e == hipSuccess) e = hipMemset(fb.p, 0, 44);
+        if ((rc = out.ensure(16)) != PTRS_OK || (rc = fb.ensure(44)) != PTRS_OK) return rc;
+        HIPCHK(hipMemset(out.p, 0, 16));
+        HIPCHK(hipMemset(fb.p, 0, 44));
         const uint32_t grid = 256u * 16u;
         const uint64_t threads = (uint64_t)grid * BLOCK, per_thread = (n_sets + threads - 1) / threads;
-        if (e == hipSuccess) { hipLaunchKernelGGL(k_selftest_div3, dim3(grid), dim3(BLOCK), 0, nullptr, seed, mode, per_thread, (unsigned long long *)out.p, (uint32_t *)fb.p); e = hipDeviceSynchronize(); }
-        if (e == hipSuccess) e = hipGetLastError();
+        hipLaunchKernelGGL(k_selftest_div3, dim3(grid), dim3(BLOCK), 0, nullptr, seed, mode, per_thread, (unsigned long long *)out.p, (uint32_t *)fb.p);
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipGetLastError());
         unsigned long long h[2] = {0, 0}; uint32_t hb[11] = {0};
-        if (e == hipSuccess) e = hipMemcpy(h, out.p, 16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hb, fb.p, 44, hipMemcpyDeviceToHost);
-        out.release(); fb.release();
-        if (e != hipSuccess) { g_err = std::string("ptrs_selftest_div3: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+        HIPCHK(hipMemcpy(h, out.p, 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hb, fb.p, 44, hipMemcpyDeviceToHost));
         *mismatches_out = h[0];
         if (fast_path_sets_out) *fast_path_sets_out = h[1];
         if (first_bad_out) std::memcpy(first_bad_out, hb, 40);
         return PTRS_OK;
     });
+}
+
+// The four probes: rows in, the kernel over them, rows out.  (inside the C-linkage block: a template needs C++ linkage)
+extern "C++" {
+template <class Launch>
+static int probe_run(PtrsScene *scene, uint32_t n, const float *rows, float *out, uint32_t w_in, uint32_t w_out, Launch launch) {
+    HIPCHK(hipSetDevice(scene->device));
+    if (n == 0) return PTRS_OK;
+    DevBuf bi, bo;
+    int rc;
+    if ((rc = bi.ensure((size_t)n * w_in * 4)) || (rc = bo.ensure((size_t)n * w_out * 4))) return rc;
+    HIPCHK(hipMemcpy(bi.p, rows, (size_t)n * w_in * 4, hipMemcpyHostToDevice));
+    launch(dim3((n + BLOCK - 1) / BLOCK), (const float *)bi.p, (float *)bo.p);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, bo.p, (size_t)n * w_out * 4, hipMemcpyDeviceToHost));
+    return PTRS_OK;
+}
 }
 
 int ptrs_probe_bsdf(PtrsScene *scene, int32_t material, const float *frame, uint32_t n, const float *rows, float *out) {
@@ -3031,18 +3063,9 @@ int ptrs_probe_bsdf(PtrsScene *scene, int32_t material, const float *frame, uint
         const int32_t kind = scene->H.mats[material].kind;
         if (kind < 0 || kind > 5) { g_err = "the BSDF probe takes Matte, Metal, Mirror, Glass, Disney or Substrate"; return PTRS_ERR_UNSUPPORTED; }
         ProbeArgs fr; std::memcpy(fr.v, frame, sizeof(fr.v));
-        HIPCHK(hipSetDevice(scene->device));
-        if (n == 0) return PTRS_OK;
-        DevBuf bi, bo;
-        int rc;
-        if ((rc = bi.ensure((size_t)n * PROBE_BSDF_IN * 4)) || (rc = bo.ensure((size_t)n * PROBE_BSDF_OUT * 4))) { bi.release(); bo.release(); return rc; }
-        hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * PROBE_BSDF_IN * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) { hipLaunchKernelGGL(k_probe_bsdf, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, scene->sc, material, kind, fr, n, (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * PROBE_BSDF_OUT * 4, hipMemcpyDeviceToHost);
-        bi.release(); bo.release();
-        if (e != hipSuccess) { g_err = std::string("ptrs_probe_bsdf: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
-        return PTRS_OK;
+        return probe_run(scene, n, rows, out, PROBE_BSDF_IN, PROBE_BSDF_OUT, [&](dim3 g, const float *i, float *o) {
+            hipLaunchKernelGGL(k_probe_bsdf, g, dim3(BLOCK), 0, nullptr, scene->sc, material, kind, fr, n, i, o);
+        });
     });
 }
 
@@ -3054,38 +3077,10 @@ int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t
         const int32_t kind = scene->H.lights[light].kind;
         if (kind != 2 && kind != 3) { g_err = "the light probe takes area (triangle) and environment lights"; return PTRS_ERR_UNSUPPORTED; }
         ProbeArgs rf{}; std::memcpy(rf.v, ref, 6 * sizeof(float));
-        HIPCHK(hipSetDevice(scene->device));
-        if (n == 0) return PTRS_OK;
-        DevBuf bi, bo;
-        int rc;
-        if ((rc = bi.ensure((size_t)n * PROBE_LIGHT_IN * 4)) || (rc = bo.ensure((size_t)n * PROBE_LIGHT_OUT * 4))) { bi.release(); bo.release(); return rc; }
-        hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * PROBE_LIGHT_IN * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) { hipLaunchKernelGGL(k_probe_light, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, scene->sc, light, rf, n, (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * PROBE_LIGHT_OUT * 4, hipMemcpyDeviceToHost);
-        bi.release(); bo.release();
-        if (e != hipSuccess) { g_err = std::string("ptrs_probe_light: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
-        return PTRS_OK;
+        return probe_run(scene, n, rows, out, PROBE_LIGHT_IN, PROBE_LIGHT_OUT, [&](dim3 g, const float *i, float *o) {
+            hipLaunchKernelGGL(k_probe_light, g, dim3(BLOCK), 0, nullptr, scene->sc, light, rf, n, i, o);
+        });
     });
-}
-
-// (inside the C-linkage block: a template needs C++ linkage)
-extern "C++" {
-template <class Launch>
-static int probe_run(PtrsScene *scene, const char *name, uint32_t n, const float *rows, float *out, uint32_t w_in, uint32_t w_out, Launch launch) {
-    HIPCHK(hipSetDevice(scene->device));
-    if (n == 0) return PTRS_OK;
-    DevBuf bi, bo;
-    int rc;
-    if ((rc = bi.ensure((size_t)n * w_in * 4)) || (rc = bo.ensure((size_t)n * w_out * 4))) { bi.release(); bo.release(); return rc; }
-    hipError_t e = hipMemcpy(bi.p, rows, (size_t)n * w_in * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch(dim3((n + BLOCK - 1) / BLOCK), (const float *)bi.p, (float *)bo.p); e = hipDeviceSynchronize(); }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * w_out * 4, hipMemcpyDeviceToHost);
-    bi.release(); bo.release();
-    if (e != hipSuccess) { g_err = std::string(name) + ": " + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
-    return PTRS_OK;
-}
 }
 
 int ptrs_probe_texture(PtrsScene *scene, int32_t tex, uint32_t n, const float *rows, float *out) {
@@ -3093,7 +3088,7 @@ int ptrs_probe_texture(PtrsScene *scene, int32_t tex, uint32_t n, const float *r
         if (!scene || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
         if (const char *why = probe_texture_check(scene->H, tex)) { g_err = why; return PTRS_ERR_INVALID; }
-        return probe_run(scene, "ptrs_probe_texture", n, rows, out, PROBE_TEX_IN, PROBE_TEX_OUT, [&](dim3 g, const float *i, float *o) {
+        return probe_run(scene, n, rows, out, PROBE_TEX_IN, PROBE_TEX_OUT, [&](dim3 g, const float *i, float *o) {
             hipLaunchKernelGGL(k_probe_texture, g, dim3(BLOCK), 0, nullptr, scene->sc, tex, n, i, o);
         });
     });
@@ -3104,7 +3099,7 @@ int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *
         if (!scene || (n && (!rows || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
         if (const char *why = probe_surface_check(scene->H, prim)) { g_err = why; return PTRS_ERR_INVALID; }
-        return probe_run(scene, "ptrs_probe_surface", n, rows, out, PROBE_SURF_IN, PROBE_SURF_OUT, [&](dim3 g, const float *i, float *o) {
+        return probe_run(scene, n, rows, out, PROBE_SURF_IN, PROBE_SURF_OUT, [&](dim3 g, const float *i, float *o) {
             hipLaunchKernelGGL(k_probe_surface, g, dim3(BLOCK), 0, nullptr, scene->sc, (uint32_t)prim, n, i, o);
         });
     });
@@ -3112,8 +3107,8 @@ int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *
 
 int ptrs_sobol_samples(const PtrsRenderParams *params, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sample_nums, const uint32_t *dims, float *out, uint64_t *index_out) {
     if (!params || (n && (!px || !py || !sample_nums || !dims || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
+    int rc = require_device();
+    if (rc != PTRS_OK) return rc;
     HIPCHK(hipSetDevice(params->device));
     if (n == 0) return PTRS_OK;
     const SampleGrid g = make_sample_grid(params->width, params->height, params->spp);
@@ -3122,26 +3117,18 @@ int ptrs_sobol_samples(const PtrsRenderParams *params, uint32_t n, const int32_t
         if (px[i] < g.min_x || px[i] >= g.min_x + g.NX || py[i] < g.min_y || py[i] >= g.min_y + g.NY) { g_err = "pixel outside the sample bounds"; return PTRS_ERR_INVALID; }
     }
     SobolDevice *sob;
-    int rc = get_sobol(params->device, &sob);
-    if (rc != PTRS_OK) return rc;
-    DSampler S;
-    S.matrices = (const uint32_t *)sob->matrices.p; S.bytetab = (const uint32_t *)sob->bytetab.p; S.nibtab = (const uint32_t *)sob->nibtab.p; S.vdc = (const uint64_t *)sob->vdc.p + (size_t)(g.log2_res - 1) * sob->stride; S.vdc_inv = (const uint64_t *)sob->vdc_inv.p + (size_t)(g.log2_res - 1) * sob->stride;
-    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
+    if ((rc = get_sobol(params->device, &sob)) != PTRS_OK) return rc;
+    const DSampler S = make_sampler(g, (const uint32_t *)sob->matrices.p, (const uint32_t *)sob->bytetab.p, (const uint32_t *)sob->nibtab.p, (const uint64_t *)sob->vdc.p + (size_t)(g.log2_res - 1) * sob->stride, (const uint64_t *)sob->vdc_inv.p + (size_t)(g.log2_res - 1) * sob->stride);
     DevBuf bx, by, bn, bdm, bo, bi;
-    auto cleanup = [&]() { bx.release(); by.release(); bn.release(); bdm.release(); bo.release(); bi.release(); };
-    if ((rc = bx.ensure((size_t)n * 4)) || (rc = by.ensure((size_t)n * 4)) || (rc = bn.ensure((size_t)n * 8)) || (rc = bdm.ensure((size_t)n * 4)) || (rc = bo.ensure((size_t)n * 4)) || (rc = bi.ensure((size_t)n * 8))) { cleanup(); return rc; }
-    hipError_t e = hipMemcpy(bx.p, px, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(by.p, py, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(bn.p, sample_nums, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(bdm.p, dims, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sobol, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, S, n, (const int32_t *)bx.p, (const int32_t *)by.p, (const uint64_t *)bn.p, (const uint32_t *)bdm.p, (float *)bo.p, (uint64_t *)bi.p);
-        e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && index_out) e = hipMemcpy(index_out, bi.p, (size_t)n * 8, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) { g_err = std::string("ptrs_sobol_samples: ") + hipGetErrorString(e); return PTRS_ERR_DEVICE; }
+    if ((rc = bx.ensure((size_t)n * 4)) || (rc = by.ensure((size_t)n * 4)) || (rc = bn.ensure((size_t)n * 8)) || (rc = bdm.ensure((size_t)n * 4)) || (rc = bo.ensure((size_t)n * 4)) || (rc = bi.ensure((size_t)n * 8))) return rc;
+    HIPCHK(hipMemcpy(bx.p, px, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(by.p, py, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bn.p, sample_nums, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bdm.p, dims, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sobol, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, S, n, (const int32_t *)bx.p, (const int32_t *)by.p, (const uint64_t *)bn.p, (const uint32_t *)bdm.p, (float *)bo.p, (uint64_t *)bi.p);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, bo.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (index_out) HIPCHK(hipMemcpy(index_out, bi.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return PTRS_OK;
 }
 

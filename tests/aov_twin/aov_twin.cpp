@@ -20,15 +20,8 @@ int aov_twin_rows(const PtrsSceneDesc *desc, const PtrsCamera *cam, float diff_s
     HostScene H;
     int rc = build_host_scene(*desc, H, g_err);
     if (rc != PTRS_OK) return rc;
-    DScene sc;
-    sc.nodes2 = H.nodes2.data(); sc.n_nodes2 = (uint32_t)H.nodes2.size(); sc.nodes4 = H.nodes4.data(); sc.n_nodes4 = (uint32_t)H.nodes4.size();
-    sc.nodes = H.nodes.data(); sc.tris = H.tris.data(); sc.shade = H.shade.data(); sc.mats = H.mats.data(); sc.texs = H.texs.data();
-    sc.levels = H.levels.data(); sc.texdata = H.texdata.data(); sc.lights = H.lights.data(); sc.distdata = H.distdata.data(); sc.inf_lights = H.inf_lights.data();
-    sc.n_nodes = (uint32_t)H.nodes.size(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
-    DCamera C;
-    std::memcpy(C.rot, cam->rot, 16); std::memcpy(C.trans, cam->trans, 12);
-    C.m00 = cam->m00; C.m11 = cam->m11; C.m22 = cam->m22; C.m23 = cam->m23;
-    std::memcpy(C.r2s, cam->raster_to_screen, 64); std::memcpy(C.dxc, cam->dx_camera, 12); std::memcpy(C.dyc, cam->dy_camera, 12);
+    const DScene sc = host_scene_view(H);
+    const DCamera C = make_camera(*cam);
     DParams R;
     std::memset(&R, 0, sizeof(R));
     R.inv_sqrt_spp = diff_scale;

@@ -25,7 +25,9 @@ int converge_twin_render_range(void *sp, const PtrsCamera *cam, const PtrsRender
     HostBackend be;
     be.stack_cap = (int)std::min<uint32_t>(s->H.stack_bound, 128u);
     const uint32_t range[2] = {sample_begin, sample_end};
-    int rc = render_impl(be, s->sc, s->H, s->H.max_depth, *cam, *prm, reinterpret_cast<v4 *>(film), sample_rgb, stats, g_err, nullptr, nullptr, nullptr, nullptr, range, reinterpret_cast<v4 *>(film_half));
+    RenderJob job;
+    job.film = reinterpret_cast<v4 *>(film); job.film_half = reinterpret_cast<v4 *>(film_half); job.samples_out = sample_rgb; job.stats = stats; job.sample_range = range;
+    int rc = render_impl(be, s->sc, s->H, s->H.max_depth, *cam, *prm, job, g_err);
     if (rc == PTRS_OK && be.overflow) { g_err = "traversal stack overflow (would corrupt LDS on the GPU)"; return PTRS_ERR_INVALID; }
     return rc;
 }

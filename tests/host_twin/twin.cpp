@@ -47,9 +47,11 @@ struct HostBackend {
     int feat = FEAT_FULL, feat_trace = FEAT_FULL;
     uint64_t nodes = 0, tris = 0;
 
-    const uint32_t *sobol_matrices() { return g_tables.matrices.data(); }
-    const uint32_t *sobol_bytetab() { return g_use_bytetab ? g_bytetab.data() : nullptr; }
-    const uint32_t *sobol_nibtab() { return nullptr; }
+    static const uint32_t *sobol_matrices() { return g_tables.matrices.data(); }
+    static const uint32_t *sobol_bytetab() { return g_use_bytetab ? g_bytetab.data() : nullptr; }
+    static const uint32_t *sobol_nibtab() { return nullptr; }
+    static const uint64_t *sobol_vdc(uint32_t row) { return g_tables.vdc.data() + (size_t)row * g_tables.stride; }
+    static const uint64_t *sobol_vdc_inv(uint32_t row) { return g_tables.vdc_inv.data() + (size_t)row * g_tables.stride; }
     std::vector<float> strat1, strat2;
     int strat_tables(int32_t NX, int32_t NY, uint32_t dim_ps, uint32_t n_dims, const float **t1, const float **t2, std::string &) {
         const size_t n = (size_t)NX * (size_t)NY * n_dims * dim_ps * dim_ps;
@@ -61,8 +63,6 @@ struct HostBackend {
         *t1 = strat1.data(); *t2 = strat2.data();
         return PTRS_OK;
     }
-    const uint64_t *sobol_vdc(uint32_t row) { return g_tables.vdc.data() + (size_t)row * g_tables.stride; }
-    const uint64_t *sobol_vdc_inv(uint32_t row) { return g_tables.vdc_inv.data() + (size_t)row * g_tables.stride; }
 
     template <class T> T *alloc(size_t n) { pool.emplace_back(n * sizeof(T) + 64); return reinterpret_cast<T *>(pool.back().data()); }
 
@@ -169,11 +169,7 @@ int twin_scene_create(const PtrsSceneDesc *d, void **out) {
     auto *s = new TwinScene();
     int rc = build_host_scene(*d, s->H, g_err);
     if (rc != PTRS_OK) { delete s; return rc; }
-    HostScene &H = s->H; DScene &sc = s->sc;
-    sc.nodes2 = H.nodes2.data(); sc.n_nodes2 = (uint32_t)H.nodes2.size(); sc.nodes4 = H.nodes4.data(); sc.n_nodes4 = (uint32_t)H.nodes4.size();
-    sc.nodes = H.nodes.data(); sc.tris = H.tris.data(); sc.shade = H.shade.data(); sc.mats = H.mats.data(); sc.texs = H.texs.data();
-    sc.levels = H.levels.data(); sc.texdata = H.texdata.data(); sc.lights = H.lights.data(); sc.distdata = H.distdata.data(); sc.inf_lights = H.inf_lights.data();
-    sc.n_nodes = (uint32_t)H.nodes.size(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
+    s->sc = host_scene_view(s->H);
     *out = s;
     return PTRS_OK;
 }
@@ -185,7 +181,9 @@ int twin_render(void *sp, const PtrsCamera *cam, const PtrsRenderParams *prm, Pt
     TwinScene *s = static_cast<TwinScene *>(sp);
     HostBackend be;
     be.stack_cap = (int)std::min<uint32_t>(s->H.stack_bound, 128u); // exactly the host's bound: the GPU sizes LDS + spill from it
-    int rc = render_impl(be, s->sc, s->H, s->H.max_depth, *cam, *prm, reinterpret_cast<v4 *>(film), sample_rgb, stats, g_err);
+    RenderJob job;
+    job.film = reinterpret_cast<v4 *>(film); job.samples_out = sample_rgb; job.stats = stats;
+    int rc = render_impl(be, s->sc, s->H, s->H.max_depth, *cam, *prm, job, g_err);
     if (rc == PTRS_OK && be.overflow) { g_err = "traversal stack overflow (would corrupt LDS on the GPU)"; return PTRS_ERR_INVALID; }
     return rc;
 }
@@ -206,15 +204,21 @@ int twin_trace_rays(void *sp, uint32_t n, const float *rays, int32_t any_hit, Pt
 
 int twin_sobol_samples(const PtrsRenderParams *prm, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sample_nums, const uint32_t *dims, float *out, uint64_t *index_out) {
     if (!g_tables.ok) { g_err = "tables not loaded"; return PTRS_ERR_INVALID; }
-    SampleGrid g = make_sample_grid(prm->width, prm->height, prm->spp);
-    DSampler S;
-    S.matrices = g_tables.matrices.data(); S.bytetab = g_use_bytetab ? g_bytetab.data() : nullptr; S.nibtab = nullptr; S.vdc = g_tables.vdc.data() + (size_t)(g.log2_res - 1) * g_tables.stride; S.vdc_inv = g_tables.vdc_inv.data() + (size_t)(g.log2_res - 1) * g_tables.stride;
-    S.log2_res = g.log2_res; S.resolution = g.resolution; S.min_x = g.min_x; S.min_y = g.min_y; S.spp = g.spp;
+    const SampleGrid g = make_sample_grid(prm->width, prm->height, prm->spp);
+    const DSampler S = make_sampler(g, HostBackend::sobol_matrices(), HostBackend::sobol_bytetab(), HostBackend::sobol_nibtab(), HostBackend::sobol_vdc(g.log2_res - 1), HostBackend::sobol_vdc_inv(g.log2_res - 1));
     for (uint32_t i = 0; i < n; ++i) {
         uint64_t idx = sobol_index(S, sample_nums[i], (uint32_t)(px[i] - g.min_x), (uint32_t)(py[i] - g.min_y));
         if (index_out) index_out[i] = idx;
         out[i] = sample_dimension(S, idx, dims[i], pixel_scramble(px[i], py[i]), px[i], py[i]);
     }
+    return PTRS_OK;
+}
+
+// pt::plan_passes as the render functions call it: {rows per pass, samples per pass, paths of the largest pass} into out3; PTRS_ERR_INVALID: "pass too large"
+int twin_plan_passes(uint64_t band_rows, uint64_t NX, uint64_t ns, uint64_t capacity, uint32_t n_lanes, int32_t paths_per_pass_given, uint64_t *out3) {
+    PassPlan p;
+    if (!plan_passes(band_rows, NX, ns, capacity, n_lanes, paths_per_pass_given != 0, p)) { g_err = "pass too large"; return PTRS_ERR_INVALID; }
+    out3[0] = p.rows_per_pass; out3[1] = p.samples_per_pass; out3[2] = p.max_paths;
     return PTRS_OK;
 }
 
@@ -260,10 +264,7 @@ int twin_surface_probe(void *sp, int32_t prim, uint32_t n, const float *rows, fl
 // generate_item and shade_item; this entry hands its rays out for the float64 comparison of tests/test_camera_film_kat.py.
 int twin_camera_rays(const PtrsCamera *cam, float diff_scale, uint32_t n, const float *pfilm, float *out) {
     if (!cam || (n && (!pfilm || !out))) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    DCamera C;
-    std::memcpy(C.rot, cam->rot, 16); std::memcpy(C.trans, cam->trans, 12);
-    C.m00 = cam->m00; C.m11 = cam->m11; C.m22 = cam->m22; C.m23 = cam->m23;
-    std::memcpy(C.r2s, cam->raster_to_screen, 64); std::memcpy(C.dxc, cam->dx_camera, 12); std::memcpy(C.dyc, cam->dy_camera, 12);
+    const DCamera C = make_camera(*cam);
     for (uint32_t i = 0; i < n; ++i) {
         const CamRay r = camera_ray(C, mk2(pfilm[2 * (size_t)i], pfilm[2 * (size_t)i + 1]), diff_scale);
         float *o = out + (size_t)i * 12;

@@ -129,3 +129,12 @@ def camera_rays(camera, diff_scale, pfilm):
     out = np.zeros((pf.shape[0], 12), dtype=np.float32)
     _check(L.twin_camera_rays(C.byref(cam), float(diff_scale), pf.shape[0], C.c_void_p(pf.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out
+
+
+def plan_passes(band_rows, nx, ns, capacity, n_lanes, paths_per_pass_given):
+    """twin_plan_passes: pt::plan_passes -> (rows per pass, samples per pass, paths of the largest pass); RuntimeError: pass too large."""
+    L = lib()
+    L.twin_plan_passes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p]
+    out = np.zeros(3, dtype=np.uint64)
+    _check(L.twin_plan_passes(int(band_rows), int(nx), int(ns), int(capacity), int(n_lanes), int(bool(paths_per_pass_given)), C.c_void_p(out.ctypes.data)))
+    return tuple(int(v) for v in out)

@@ -71,6 +71,28 @@ def test_twin_pass_and_band_decomposition(ptrs, orc):
     assert np.array_equal(film["weight"].view(np.uint32), film_full["weight"].view(np.uint32))
 
 
+# capacity, lanes, samples, paths_per_pass given -> rows per pass, samples per pass; a band of 20 sample rows x NX = 36 (720 paths per sample).
+# By hand from the expressions render_impl and the AOV call both held before they shared pt::plan_passes.
+PLAN_CASES = [
+    (1 << 27, 1, 8, False, 20, 8),  # everything fits: one pass
+    (2000, 1, 8, True, 20, 2),      # two samples of the band fit: four equal sample chunks
+    (500, 1, 8, True, 10, 1),       # not one sample of the band: 13 rows would fit, two equal row blocks
+    (36, 1, 8, True, 1, 1),         # a request of 10 raised to NX: one row per pass
+    (1 << 27, 4, 8, False, 20, 2),  # four lanes: the one chunk becomes four
+    (1 << 27, 4, 6, False, 20, 2),  # ... also where they cannot be equal
+    (1 << 27, 4, 2, False, 20, 2),  # fewer samples than lanes: no rounding
+    (2000, 4, 8, True, 20, 2),      # paths_per_pass given: the lane rounding is skipped
+]
+
+
+def test_twin_plan_passes():
+    for capacity, lanes, ns, given, rows, samples in PLAN_CASES:
+        assert twin.plan_passes(20, 36, ns, capacity, lanes, given) == (rows, samples, rows * 36 * samples), (capacity, lanes, ns, given)
+    assert twin.plan_passes(65536, 65535, 1, 1 << 32, 1, False) == (65536, 1, 65536 * 65535)  # 2^32 - 65536 paths: the last row count that passes
+    with pytest.raises(RuntimeError, match="pass too large"):
+        twin.plan_passes(65537, 65535, 1, 1 << 32, 1, False)  # rows x NX x samples = 2^32 - 1
+
+
 def test_twin_sobol(orc):
     rng = np.random.default_rng(4)
     p = orc.make_params(1024, 1024, 256, 15)
