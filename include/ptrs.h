@@ -489,6 +489,19 @@ int ptrs_probe_light(PtrsScene *scene, int32_t light, const float *ref, uint32_t
  * rx_d.xyz, ry_d.xyz, w.xyz); out: n x 64 floats in the layout of csrc/pt_probe.h surface_probe_row. */
 int ptrs_probe_texture(PtrsScene *scene, int32_t tex, uint32_t n, const float *rows, float *out);
 int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *rows, float *out);
+/* ptrs_probe_math: the arithmetic substrate itself on device `device`, one function call per row, no scene.  rows: n x 16 floats,
+ * out: n x 16 floats, raw results (an integer travels as the bit pattern of a float), unused columns 0.  A NULL buffer, n == 0, an
+ * unknown op or more than PTRS_PROBE_MAX_ROWS rows are refused before a device is touched.  op (csrc/pt_probe.h math_probe_row):
+ *   0 pt_sinf  1 pt_cosf  2 pt_sincosf (sin, cos)  3 pt_tanf  4 pt_logf  5 pt_log2f  6 pt_expf  7 pt_powf(in0, in1)
+ *   8 pt_atan2f(y = in0, x = in1)  9 pt_acosf  10 in0 / in1  11 sqrt_  12 floor_, ceil_, max0_, clamp_(in0, in1, in2)
+ *   13 max_, min_  14 max_nz, min_nz  15 (float)bits(in0) * 2^-32, then min_nz(1 - eps, .)
+ *   16 f2i_sat(in0), inc_wrap(bits(in1)), abs_mod(bits(in2), bits(in3))
+ *   17 next_float_up(in0), next_float_down(in0), gamma_err(bits(in1)), power_heuristic(in2, in3)
+ *   18 solve_2x2(in0..3, in4, in5): solved, x0, x1
+ *   19 v = in0..2: normalize, coordinate_system v2, v3, spherical_theta, spherical_phi
+ *   20 p, p_error, n, w (in0..11): offset_ray_origin, spawn_pair plus, minus, spawn_from
+ *   21 u = in0, size = bits(in1) in 2..14, cdf = in2..: find_interval_cdf, find_interval_cdf_guided (guide table built from the cdf) */
+int ptrs_probe_math(int32_t device, uint32_t op, uint32_t n, const float *rows, float *out);
 
 #ifdef __cplusplus
 }

@@ -62,7 +62,8 @@ PT_HD double ptd_sin_poly(double r) {
                  S8 = 1.0 / 355687428096000.0;
     double z = r * r;
     double p = S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * (S6 + z * (S7 + z * S8))))));
-    return r + r * (z * p);
+    double s = r + r * (z * p);
+    return r == 0.0 ? r : s; /* sin(-0) = -0: the sum is -0 + (-0 * -0) = +0.  (r is zero only for x = +-0.) */
 }
 
 PT_HD double ptd_cos_poly(double r) {
@@ -170,6 +171,11 @@ PT_HD double ptd_exp(double x) {
     return p * ptd_pow2i(ki);
 }
 
+/* pow for the bases a renderer raises: x >= +0, +inf included, where it is C99's pow.  Restrictions (C99 F.9.4.4 says otherwise; the
+ * fixture of tests/test_math_kat.py lists every such row by value and holds device and host to the answers given here):
+ *   - a negative base, -inf included, gives NaN whatever y is (C99: defined for integer and infinite y);
+ *   - -0 is treated as +0 (C99: the sign of the zero carries over for odd integer y);
+ *   - pow(1, NaN) is NaN (C99: 1). */
 PT_HD double ptd_pow(double x, double y) {
     if (y == 0.0) return 1.0;
     if (ptd_isnan(x) || ptd_isnan(y)) return ptd_nan();
@@ -231,7 +237,9 @@ PT_HD double ptd_atan2(double y, double x) {
     return ysign ? -a : a;
 }
 
-/* sqrt in binary64: the hardware/OCML operation is correctly rounded on x86-64 and gfx950 */
+/* sqrt in binary64: x86-64's instruction is correctly rounded; hipcc's gfx950 expansion returned the same bits wherever it was asked:
+ * tests/test_math_kat.py holds pt_acosf, which takes its root here, to the exact value rounded once on both (|x| next to 1 among
+ * its arguments).  The binary64 operation has no direct test of its own. */
 PT_HD double ptd_sqrt(double x) { return __builtin_sqrt(x); }
 
 PT_HD double ptd_acos(double x) {

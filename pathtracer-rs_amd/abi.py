@@ -18,6 +18,11 @@ SAMPLER_SOBOL, SAMPLER_STRATIFIED = 0, 1
 PtrsAovAlbedo, PtrsAovNormal, PtrsAovDepth = 1, 2, 4
 PtrsAovPlanes, PtrsAovSampleFloats = 3, 12
 PtrsAovNames = ("albedo", "normal", "depth")
+# ptrs_probe_math: the ops of csrc/pt_probe.h math_probe_row, floats per row (in and out), the entry point's signature
+(MATH_SIN, MATH_COS, MATH_SINCOS, MATH_TAN, MATH_LOG, MATH_LOG2, MATH_EXP, MATH_POW, MATH_ATAN2, MATH_ACOS, MATH_DIV, MATH_SQRT,
+ MATH_ROUND, MATH_MINMAX, MATH_MINMAX_NZ, MATH_U2F, MATH_INT, MATH_NEXT, MATH_SOLVE, MATH_FRAME, MATH_SPAWN, MATH_SEARCH, MATH_NUM_OPS) = range(23)
+PROBE_MATH_WIDTH = 16
+PROBE_MATH_ARGTYPES = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)

@@ -1,5 +1,5 @@
-// pt_probe.h -- per-row probes of one material's BSDF, of one light, of one texture and of one triangle's hit surface, for
-// known-answer tests only.
+// pt_probe.h -- per-row probes of one material's BSDF, of one light, of one texture, of one triangle's hit surface and of the
+// arithmetic substrate itself (include/ptrs_detmath.h, pt_vec.h), for known-answer tests only.
 //
 // The render kernels never include this file.  The gfx950 test entry points (ptrs_probe_bsdf /
 // ptrs_probe_light) and the host twin run exactly these functions, so a test can evaluate the
@@ -14,7 +14,7 @@
 namespace pt {
 
 enum : uint32_t { PROBE_BSDF_IN = 8, PROBE_BSDF_OUT = 16, PROBE_LIGHT_IN = 5, PROBE_LIGHT_OUT = 16, PROBE_TEX_IN = 6, PROBE_TEX_OUT = 8,
-                  PROBE_SURF_IN = 16, PROBE_SURF_OUT = 64 };
+                  PROBE_SURF_IN = 16, PROBE_SURF_OUT = 64, PROBE_MATH_IN = 16, PROBE_MATH_OUT = 16 };
 
 // A synthetic hit for a BSDF probe: geometric normal ng, shading normal ns, shading dpdu (the
 // bsdf's ss = normalize(dpdu), ts = ns x ss: the caller passes dpdu orthogonal to ns).
@@ -135,6 +135,95 @@ PT_HD void surface_probe_row(const DScene &sc, uint32_t prim, const float *in, f
     const f3 w[3] = {sp.plus, sp.minus, ow};
     for (int k = 0; k < 3; ++k) { out[40 + 3 * k] = w[k].x; out[41 + 3 * k] = w[k].y; out[42 + 3 * k] = w[k].z; }
     out[49] = (float)steps;
+}
+
+// The arithmetic substrate, one call per row: the transcendental stand-ins of include/ptrs_detmath.h, the binary32 helpers of
+// pt_vec.h and the two cdf searches, at arguments of the test's choosing.  Every output is the raw result of the function named (an
+// integer travels as the bit pattern of a float, as guide[] does); unused columns are 0.  A row is PROBE_MATH_IN floats in,
+// PROBE_MATH_OUT floats out (the composites need twelve of each).
+enum : uint32_t {
+    MATH_SIN = 0, MATH_COS, MATH_SINCOS, MATH_TAN, MATH_LOG, MATH_LOG2, MATH_EXP, MATH_POW, MATH_ATAN2, MATH_ACOS, // pt_*f of in[0] (in[0], in[1])
+    MATH_DIV,      // in[0] / in[1]
+    MATH_SQRT,     // sqrt_(in[0])
+    MATH_ROUND,    // floor_(in[0]), ceil_(in[0]), max0_(in[0]), clamp_(in[0], in[1], in[2])
+    MATH_MINMAX,   // max_(in[0], in[1]), min_(in[0], in[1])
+    MATH_MINMAX_NZ, // max_nz(in[0], in[1]), min_nz(in[0], in[1]) (domain: no +0 / -0 tie)
+    MATH_U2F,      // v = bits(in[0]): (float)v * 0x1p-32f, then min_nz(PT_ONE_MINUS_EPS, .) as sobol_sample ends
+    MATH_INT,      // f2i_sat(in[0]), inc_wrap(bits(in[1])), abs_mod(bits(in[2]), bits(in[3])) (0 unless the modulus is positive)
+    MATH_NEXT,     // next_float_up(in[0]), next_float_down(in[0]), gamma_err(bits(in[1])), power_heuristic(in[2], in[3])
+    MATH_SOLVE,    // solve_2x2(in[0..3] row-major, in[4], in[5]): solved, x0, x1
+    MATH_FRAME,    // v = in[0..2]: normalize(v) 0-2, coordinate_system(v) v2 3-5, v3 6-8, spherical_theta(v) 9, spherical_phi(v) 10
+    MATH_SPAWN,    // p 0-2, p_error 3-5, n 6-8, w 9-11: offset_ray_origin 0-2, spawn_pair plus 3-5, minus 6-8, spawn_from(w) 9-11
+    MATH_SEARCH,   // u = in[0], size = bits(in[1]) in 2..14, cdf = in[2 .. 2 + size): find_interval_cdf, find_interval_cdf_guided
+    MATH_NUM_OPS
+};
+PT_HD void math_probe_row(uint32_t op, const float *in, float *out) {
+    for (uint32_t k = 0; k < PROBE_MATH_OUT; ++k) out[k] = 0.0f;
+    const float a = in[0], b = in[1];
+    switch (op) {
+        case MATH_SIN: out[0] = pt_sinf(a); break;
+        case MATH_COS: out[0] = pt_cosf(a); break;
+        case MATH_SINCOS: pt_sincosf(a, &out[0], &out[1]); break;
+        case MATH_TAN: out[0] = pt_tanf(a); break;
+        case MATH_LOG: out[0] = pt_logf(a); break;
+        case MATH_LOG2: out[0] = pt_log2f(a); break;
+        case MATH_EXP: out[0] = pt_expf(a); break;
+        case MATH_POW: out[0] = pt_powf(a, b); break;
+        case MATH_ATAN2: out[0] = pt_atan2f(a, b); break;
+        case MATH_ACOS: out[0] = pt_acosf(a); break;
+        case MATH_DIV: out[0] = a / b; break;
+        case MATH_SQRT: out[0] = sqrt_(a); break;
+        case MATH_ROUND: out[0] = floor_(a); out[1] = ceil_(a); out[2] = max0_(a); out[3] = clamp_(a, b, in[2]); break;
+        case MATH_MINMAX: out[0] = max_(a, b); out[1] = min_(a, b); break;
+        case MATH_MINMAX_NZ: out[0] = max_nz(a, b); out[1] = min_nz(a, b); break;
+        case MATH_U2F: { const uint32_t v = ptf_bits(a); out[0] = (float)v * 0x1p-32f; out[1] = min_nz(PT_ONE_MINUS_EPS, (float)v * 0x1p-32f); break; }
+        case MATH_INT: {
+            const int32_t m = (int32_t)ptf_bits(in[3]);
+            out[0] = ptf_from_bits((uint32_t)f2i_sat(a));
+            out[1] = ptf_from_bits((uint32_t)inc_wrap((int32_t)ptf_bits(b)));
+            out[2] = ptf_from_bits(m > 0 ? (uint32_t)abs_mod((int32_t)ptf_bits(in[2]), m) : 0u);
+            break;
+        }
+        case MATH_NEXT: out[0] = next_float_up(a); out[1] = next_float_down(a); out[2] = gamma_err((int32_t)ptf_bits(b)); out[3] = power_heuristic(in[2], in[3]); break;
+        case MATH_SOLVE: {
+            float x0 = 0.0f, x1 = 0.0f;
+            const bool ok = solve_2x2(in[0], in[1], in[2], in[3], in[4], in[5], x0, x1);
+            out[0] = ok ? 1.0f : 0.0f; out[1] = x0; out[2] = x1;
+            break;
+        }
+        case MATH_FRAME: {
+            const f3 v = mk3(in[0], in[1], in[2]), nv = normalize(v);
+            f3 v2, v3;
+            coordinate_system(v, v2, v3);
+            out[0] = nv.x; out[1] = nv.y; out[2] = nv.z; out[3] = v2.x; out[4] = v2.y; out[5] = v2.z; out[6] = v3.x; out[7] = v3.y; out[8] = v3.z;
+            out[9] = spherical_theta(v); out[10] = spherical_phi(v);
+            break;
+        }
+        case MATH_SPAWN: {
+            const f3 p = mk3(in[0], in[1], in[2]), pe = mk3(in[3], in[4], in[5]), n = mk3(in[6], in[7], in[8]), w = mk3(in[9], in[10], in[11]);
+            const SpawnPair sp = spawn_pair(p, pe, n);
+            const f3 v[4] = {offset_ray_origin(p, pe, n, w), sp.plus, sp.minus, spawn_from(sp, w)};
+            for (int k = 0; k < 4; ++k) { out[3 * k] = v[k].x; out[3 * k + 1] = v[k].y; out[3 * k + 2] = v[k].z; }
+            break;
+        }
+        case MATH_SEARCH: {
+            uint32_t size = ptf_bits(b);
+            size = size < 2u ? 2u : (size > 14u ? 14u : size);
+            float cdf[14], guide[17];
+            for (uint32_t k = 0; k < 14u; ++k) cdf[k] = k < size ? in[2u + k] : 0.0f;
+            const uint32_t g = size - 1u <= 8u ? 8u : 16u; // the guide table as build_host_scene lays it out
+            uint32_t cnt = 0;
+            for (uint32_t k = 0; k <= g; ++k) {
+                const float x = (float)k / (float)g;
+                while (cnt < size && cdf[cnt] <= x) ++cnt;
+                guide[k] = ptf_from_bits(cnt);
+            }
+            out[0] = ptf_from_bits(find_interval_cdf(cdf, size, a));
+            out[1] = ptf_from_bits(find_interval_cdf_guided(cdf, size, a, guide, g));
+            break;
+        }
+        default: break;
+    }
 }
 
 // The argument checks of the texture / surface probes that need the scene (the device entry points and the host twin make the same

@@ -1538,6 +1538,11 @@ __global__ __launch_bounds__(BLOCK) void k_probe_surface(DScene sc, uint32_t pri
     if (i >= n) return;
     surface_probe_row(sc, prim, in + (uint64_t)i * PROBE_SURF_IN, out + (uint64_t)i * PROBE_SURF_OUT);
 }
+__global__ __launch_bounds__(BLOCK) void k_probe_math(uint32_t op, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    math_probe_row(op, in + (uint64_t)i * PROBE_MATH_IN, out + (uint64_t)i * PROBE_MATH_OUT);
+}
 
 // ---- device buffers ---------------------------------------------------------------------------------
 // Owns its block: the destructor frees it, so a scene, a denoiser or an entry point's locals need no release list and an early return
@@ -3102,6 +3107,23 @@ int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *
         return probe_run(scene, n, rows, out, PROBE_SURF_IN, PROBE_SURF_OUT, [&](dim3 g, const float *i, float *o) {
             hipLaunchKernelGGL(k_probe_surface, g, dim3(BLOCK), 0, nullptr, scene->sc, (uint32_t)prim, n, i, o);
         });
+    });
+}
+
+int ptrs_probe_math(int32_t device, uint32_t op, uint32_t n, const float *rows, float *out) {
+    return guarded([&]() -> int {
+        if (!rows || !out || n == 0 || op >= MATH_NUM_OPS) { g_err = "bad math probe request"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        int rc = select_device(device);
+        if (rc != PTRS_OK) return rc;
+        DevBuf bi, bo;
+        if ((rc = bi.ensure((size_t)n * PROBE_MATH_IN * 4)) != PTRS_OK || (rc = bo.ensure((size_t)n * PROBE_MATH_OUT * 4)) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(bi.p, rows, (size_t)n * PROBE_MATH_IN * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_probe_math, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, op, n, (const float *)bi.p, (float *)bo.p);
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(out, bo.p, (size_t)n * PROBE_MATH_OUT * 4, hipMemcpyDeviceToHost));
+        return PTRS_OK;
     });
 }
 

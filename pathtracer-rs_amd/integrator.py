@@ -624,6 +624,17 @@ def probe_surface(scene, prim, rows, device=0):
     return out
 
 
+def probe_math(op, rows, device=0):
+    """ptrs_probe_math: op `op` (abi.MATH_*) of the arithmetic substrate on every row (n x 16 floats) -> (n x 16) raw results in the
+    layout of csrc/pt_probe.h math_probe_row; integers travel as bit patterns."""
+    L = load_library()
+    L.ptrs_probe_math.argtypes = abi.PROBE_MATH_ARGTYPES
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, abi.PROBE_MATH_WIDTH)
+    out = np.zeros((rows.shape[0], abi.PROBE_MATH_WIDTH), dtype=np.float32)
+    _check(L.ptrs_probe_math(int(device), int(op), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def build_id():
     """ptrs_build_id: hash of the kernel sources and compiler flags the loaded library was built from (build.source_hash)."""
     return load_library().ptrs_build_id().decode()

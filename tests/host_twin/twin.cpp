@@ -260,6 +260,13 @@ int twin_surface_probe(void *sp, int32_t prim, uint32_t n, const float *rows, fl
     return PTRS_OK;
 }
 
+int twin_math_probe(uint32_t op, uint32_t n, const float *rows, float *out) {
+    if (!rows || !out || n == 0 || op >= MATH_NUM_OPS) { g_err = "bad math probe request"; return PTRS_ERR_INVALID; }
+    if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) math_probe_row(op, rows + (size_t)i * PROBE_MATH_IN, out + (size_t)i * PROBE_MATH_OUT);
+    return PTRS_OK;
+}
+
 // pt::camera_ray once per row: p_film (n x 2) -> o, d, rx_d, ry_d (n x 12).  The render kernels reach the same function through
 // generate_item and shade_item; this entry hands its rays out for the float64 comparison of tests/test_camera_film_kat.py.
 int twin_camera_rays(const PtrsCamera *cam, float diff_scale, uint32_t n, const float *pfilm, float *out) {

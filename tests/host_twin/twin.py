@@ -120,6 +120,16 @@ def surface_probe(scene, prim, rows):
     return out
 
 
+def math_probe(op, rows):
+    """twin_math_probe: ptrs_probe_math's rows on the CPU (n x 16 in, n x 16 out; csrc/pt_probe.h math_probe_row)."""
+    L = lib()
+    L.twin_math_probe.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 16)
+    out = np.zeros((rows.shape[0], 16), dtype=np.float32)
+    _check(L.twin_math_probe(int(op), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def camera_rays(camera, diff_scale, pfilm):
     """twin_camera_rays: pt::camera_ray for every p_film row (n x 2) -> (n x 12): o, d, rx_d, ry_d."""
     L = lib()

@@ -138,3 +138,30 @@ def test_texture_and_surface_probes_check_their_arguments(ptrs):
     assert T.twin_surface_probe(ts._h, 1, 1, buf, buf) != 0                # no such triangle
     assert T.twin_surface_probe(ts._h, 0, 1, buf, None) != 0               # out missing
     assert T.twin_texture_probe(ts._h, 0, 1, buf, buf) == 0 and T.twin_surface_probe(ts._h, 0, 1, buf, buf) == 0
+
+
+def test_math_probe_checks_its_arguments(ptrs):
+    """ptrs_probe_math refuses a missing buffer, no rows, an unknown op and too many rows before it touches a device (no GPU needed);
+    the host twin's copy makes the same checks, and the binding's op list ends where the header's does."""
+    assert "ptrs_probe_math" in _declared_functions()
+    L = ptrs.load_library()
+    L.ptrs_probe_math.argtypes = ptrs.abi.PROBE_MATH_ARGTYPES
+    import twin
+    T = twin.lib()
+    T.twin_math_probe.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    buf = (C.c_float * 16)()
+    n_ops = ptrs.abi.MATH_NUM_OPS
+    for fn in (lambda *a: L.ptrs_probe_math(0, *a), T.twin_math_probe):
+        assert fn(0, 1, None, buf) != 0                # rows missing
+        assert fn(0, 1, buf, None) != 0                # out missing
+        assert fn(0, 0, buf, buf) != 0                 # nothing to do
+        assert fn(n_ops, 1, buf, buf) != 0             # no such op
+        assert fn(0xffffffff, 1, buf, buf) != 0
+        assert fn(0, (1 << 24) + 1, buf, buf) != 0     # more rows than one launch takes
+    for err in (L.ptrs_last_error(), T.twin_last_error()):
+        assert b"too many probe rows" in err
+    assert L.ptrs_probe_math(0, n_ops, 1, buf, buf) != 0 and b"bad math probe request" in L.ptrs_last_error()
+    assert T.twin_math_probe(n_ops - 1, 1, buf, buf) == 0 and T.twin_math_probe(0, 1, buf, buf) == 0
+    text = open(os.path.join(ROOT, "pathtracer-rs_amd", "csrc", "pt_probe.h")).read()
+    ops = re.search(r"MATH_SIN = 0,(.*?)MATH_NUM_OPS", text, flags=re.S).group(1)
+    assert len(re.findall(r"\bMATH_[A-Z0-9_]+\b", "MATH_SIN," + re.sub(r"//.*", "", ops))) == n_ops

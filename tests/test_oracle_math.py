@@ -58,6 +58,9 @@ def test_detmath_is_correctly_rounded_on_samples(orc):
     got = np.array([L.orc_detmath(6, float(y), float(x)) for y, x in zip(ys, xs)], dtype=np.float32)
     assert np.array_equal(got, np.arctan2(ys.astype(np.float64), xs.astype(np.float64)).astype(np.float32))
     assert L.orc_detmath(6, 0.0, -1.0) == float(np.float32(math.pi))
+    xs, ys = rng.uniform(1e-3, 1, 20000).astype(np.float32), rng.uniform(1e-2, 50, 20000).astype(np.float32)
+    got = np.array([L.orc_detmath(5, float(x), float(y)) for x, y in zip(xs, ys)], dtype=np.float32)
+    assert np.array_equal(got, np.power(xs.astype(np.float64), ys.astype(np.float64)).astype(np.float32))
 
 
 def test_fused_sincos_equals_sin_and_cos(orc):
