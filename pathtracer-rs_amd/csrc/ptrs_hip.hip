@@ -1,4 +1,5 @@
-// ptrs_hip.hip -- gfx950 (MI355X) kernels and the C ABI of include/ptrs.h.
+// ptrs_hip.hip -- gfx950 (MI355X) kernels and the C ABI of include/ptrs.h: the one translation unit hipcc is given.  The queue
+// primitives (pt_hip_queue.h) and the kernels outside the path loop (pt_hip_post.h) are included at their places in the definition order.
 //
 // One wavefront stage = one kernel.  Every queue-driven kernel is PERSISTENT: a launch holds the workgroups that fit the machine at
 // once (256 threads = 4 wave64 each), and each WAVE works through queue segments -- one wave per segment -- that it takes from the
@@ -86,62 +87,7 @@ const OptionDesc k_options[] = {
         }                                                                                                         \
     } while (0)
 
-constexpr int BLOCK = 256, WAVES = BLOCK / 64;
-
-// Segmented queues, one WAVE per segment.  Every queue of a pass is split into G segments; the wave that consumes segment s of
-// one stage appends only to segment s of the next, so a segment has one writer at a time and its slots come from a counter the
-// wave keeps in a scalar register (one s_bcnt1 per push): no atomics on the data path at all, neither global (the first version:
-// ~16 M returning atomics per frame on one address) nor LDS (round 2: one ds_add per wave and push, plus a workgroup barrier
-// per segment).  The queue kernels are PERSISTENT: a launch holds only as many workgroups as fit the machine at once
-// (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs), and each of their waves takes segment numbers from a per-launch ticket
-// counter until the G segments are gone (one returning global atomic per wave and segment, asked for one segment ahead).  With a
-// workgroup per segment and G = 2048 workgroups on 5-7 resident per CU, the second scheduling round of every launch ran a third
-// full (time-average occupancy 8 / ceil(8 / c) waves per SIMD); now every wave slot works until the tickets run out, and the
-// tail is one wave-segment (G / resident waves is 1.3-2.7 at the default grid_mult).
-__device__ inline uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ inline uint32_t lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); } // set bits of m below this lane
-__device__ inline uint32_t wave_push(uint32_t &count, bool pred) { // slot for every lane with pred; count is wave-uniform
-    const unsigned long long m = __ballot(pred);
-    const uint32_t slot = count + lanes_below(m);
-    count += (uint32_t)__popcll(m);
-    return slot;
-}
-// The segment a wave works on next, or a number >= G when the launch has none left.  One counter for the whole launch would take one
-// returning atomic per segment on ONE address, ~18 ns apiece on MI355X: 0.3 ms for G = 16384, which is what a kernel of the thin late
-// rounds of a pass then costs however little it has to do (measured: 11 of Cornell's 16 rounds, 30 ms of a 200 ms frame).  So the
-// launch has TK_SUB counters 128 bytes apart, each handing out a contiguous range of ceil(G / TK_SUB) segments; a wave reads all of
-// them with one load (lane k reads counter k), takes a ticket from the first open one at or after its home counter, and moves on as
-// ranges run out.  The atomics of a launch spread over TK_SUB addresses, and a wave sees the launch exhausted with a single load.
-enum : uint32_t { TK_SUB = 64, TK_SUB_STRIDE = 32, TK_LAUNCH_WORDS = TK_SUB * TK_SUB_STRIDE };
-__device__ inline uint32_t seg_next(uint32_t *ticket, uint32_t G) {
-    const uint32_t per = (G + TK_SUB - 1u) / TK_SUB; // every counter hands out `per` numbers; those at or beyond G (the last counters' surplus) are skipped
-    const uint32_t home = (blockIdx.x * WAVES + (threadIdx.x >> 6)) & (TK_SUB - 1u);
-    for (;;) {
-        // lane k reads counter k (a device-coherent load: the counters only grow, a stale value costs one atomic that comes back empty); which
-        // counters are still open is a lane mask.  In one asm statement with one temporary: written in C++ the scan's per-lane values are
-        // hoisted out of the callers' segment loops and cost every kernel ~10 vector registers.
-        uint32_t tmp; unsigned long long open;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshlrev_b32 %0, 7, %0\n\tglobal_load_dword %0, %0, %2 sc1\n\ts_waitcnt vmcnt(0)\n\tv_cmp_gt_u32 %1, %3, %0"
-                     : "=&v"(tmp), "=s"(open) : "s"(ticket), "s"(per) : "memory");
-        static_assert(TK_SUB_STRIDE * 4u == 128u, "the asm above shifts the lane id by 7");
-        if (open == 0ull) return 0xffffffffu;
-        const unsigned long long rot = home ? ((open >> home) | (open << (64u - home))) : open; // the home counter first
-        const uint32_t c = (home + (uint32_t)__ffsll((long long)rot) - 1u) & (TK_SUB - 1u);
-        uint32_t t = 0;
-        if (__lane_id() == 0) t = atomicAdd(ticket + c * TK_SUB_STRIDE, 1u);
-        t = rfl(t);
-        const uint32_t s = c * per + t;
-        if (t < per && s < G) return s;
-        // the counter ran out between the load and the atomic, or the number is one of its surplus: look again
-    }
-}
-// counts[(row * Q_STRIDE + q) * G + s]
-__device__ inline uint32_t *seg_count(const DQueues &Q, uint32_t row, int q, uint32_t G, uint32_t s) { return Q.counts + ((size_t)row * Q_STRIDE + (size_t)q) * G + s; }
-enum { TK_EXTEND = 0, TK_CONNECT = 1, TK_SHADE0 = 2, TK_EPILOGUE = 9, TK_RESOLVE = 10, TK_PRESAMPLE = 11, TK_TAIL = 12 }; // tickets[(row * Q_STRIDE + TK_*) * TK_LAUNCH_WORDS]: the counters of one launch of a pass
-// A round nobody reaches (every path has ended: rounds are enqueued without asking, and for scenes with null-BSDF skips a few more
-// than max_depth + 1) costs its launches only: each kernel looks at the flag and leaves.
-// (Q.alive[row]: the round's "some path is still alive" flag, set by the shade kernels of the round before)
-__device__ inline bool round_is_dead(const DQueues &Q, uint32_t it) { return it > 0u && rfl(Q.alive[it]) == 0u; }
+#include "pt_hip_queue.h"
 
 // Geometry sources of the traversal kernels.  LDS pointers keep their address space in the type: with two generic pointers the
 // compiler folds both paths into one generic-address (flat) load, which is slower than either.
@@ -222,7 +168,7 @@ struct LdsStack { // records are packed into one 64-bit word (ref | entry distan
 //             range runs dry its waves move on to the next counter's (the neighbouring region).  Placement is a matter of speed only.
 // Either way a segment's entries are compact (positions e0 .. e0 + n) and hold at most seg_cap = ceil(chunks / G) x 64 paths.
 __global__ __launch_bounds__(BLOCK) void k_generate(DParams R, DSampler S, DCamera C, DPaths P, DQueues Q, uint32_t seg_cap, uint32_t G, uint32_t deal) {
-    const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, s = wave_of_launch();
     if (s >= G) return;
     const uint32_t chunks = (R.n_paths + 63u) / 64u;
     const uint32_t e0 = s * seg_cap; // the segment's first position in the queue-ordered arrays
@@ -426,14 +372,19 @@ __device__ inline bool lf_leaf_step(const DScene &sc, uint32_t &leaf, f3 op, flo
     out.prim = ok ? (any_rt ? 0 : (int32_t)prim) : out.prim; out.t = ok ? h.t : out.t; out.b0 = ok ? h.b0 : out.b0; out.b1 = ok ? h.b1 : out.b1; out.b2 = ok ? h.b2 : out.b2; out.flags = ok ? flags : out.flags;
     return ok & any_rt;
 }
+// The vote of rf_step / lf_step: which lanes of the wave wait for a node visit and which for a triangle test; true when the visit has the majority.
+__device__ inline bool vote_node_phase(uint32_t r_cur, bool &at_node, bool &at_leaf) {
+    at_node = (int32_t)r_cur >= 0; at_leaf = (int32_t)r_cur < -1; // leaf references have bit 31 set; lanes without a ray hold REF_NONE = -1
+    const uint32_t n_node = rfl((uint32_t)__popcll(__ballot(at_node))), n_leaf = rfl((uint32_t)__popcll(__ballot(at_leaf))); // (scalar registers: the comparison is an s_cmp)
+    return n_node >= n_leaf;
+}
 // rf_step for the LDS form (vote: the phase most lanes are in, one visit or one triangle; else descend to a leaf, then its triangles)
 template <bool VOTE, bool ALPHA, class Stack>
 __device__ inline void lf_step(const DScene &sc, uint32_t &r_cur, f3 l_o, f3 l_inv, f3 l_op, float l_sx, float l_sy, float l_sz, uint32_t l_ox, uint32_t l_oy, uint32_t l_oz, uint32_t l_neg, uint32_t l_tri,
                                float &r_tmax, HitRec &r_h, bool &r_hit, Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n) {
     if (VOTE) {
-        const bool at_node = (int32_t)r_cur >= 0, at_leaf = (int32_t)r_cur < -1; // leaf references have bit 31 set; lanes without a ray hold REF_NONE = -1
-        const uint32_t n_node = rfl((uint32_t)__popcll(__ballot(at_node))), n_leaf = rfl((uint32_t)__popcll(__ballot(at_leaf))); // (scalar registers: the comparison is an s_cmp)
-        if (n_node >= n_leaf) {
+        bool at_node, at_leaf;
+        if (vote_node_phase(r_cur, at_node, at_leaf)) {
             if (at_node) { PT_COUNT_NODE(sc_n) lf_node_visit(r_cur, l_o, l_inv, l_ox, l_oy, l_oz, l_neg, r_tmax, stk, nn); }
         } else if (at_leaf) {
             PT_COUNT_TRI(sc_n, 1u)
@@ -475,9 +426,8 @@ template <bool VOTE, bool QUAD, bool ALPHA, class Stack, class Geom>
 __device__ inline void rf_step(const Geom &G, const DScene &sc, uint32_t &r_cur, f3 r_o, f3 r_inv, const bool r_neg[3], uint32_t r_nb3, uint32_t r_px, uint32_t r_py, uint32_t r_pz, const RayShear &r_shear, float &r_tmax, HitRec &r_h, bool &r_hit,
                                Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n) {
     if (VOTE) {
-        const bool at_node = (int32_t)r_cur >= 0, at_leaf = (int32_t)r_cur < -1; // leaf references have bit 31 set; lanes without a ray hold REF_NONE = -1
-        const uint32_t n_node = rfl((uint32_t)__popcll(__ballot(at_node))), n_leaf = rfl((uint32_t)__popcll(__ballot(at_leaf))); // (scalar registers: the comparison is an s_cmp)
-        if (n_node >= n_leaf) {
+        bool at_node, at_leaf;
+        if (vote_node_phase(r_cur, at_node, at_leaf)) {
             if (at_node) { PT_COUNT_NODE(sc_n) node_visit<QUAD, false>(G, r_cur, r_o, r_inv, r_neg, r_tmax, stk, nn, r_nb3, r_px, r_py, r_pz); }
         } else if (at_leaf) {
             PT_COUNT_TRI(sc_n, 1u)
@@ -560,6 +510,18 @@ static_assert((uint32_t)PTRS_QUAD_WAVES * lds_alloc(trav_lds_bytes<8, 0>()) <= (
 #define PT_XS(k)
 #define PT_XS_COUNT(k, v)
 #endif
+// What k_extend_rf, k_connect_rf and k_tail do alike around their segments.  The prologue: the tree's top or the whole LDS form into the
+// kernel's staging area (the __shared__ arrays and the barrier that makes the copy visible stay with the kernel).  The last line: the
+// thread's traversal counters into the render's statistics.
+template <int DEPTH, int GEOM>
+__device__ inline void stage_geometry(const DScene &sc, v4 *lds_geom, GeomTop &GG, LdsGeom &LG) {
+    LG.root = LG.tri0 = LG.tri_copy = 0;
+    GG = stage_top(sc, lds_geom, TravLds<DEPTH, GEOM>::TOP);
+    if (GEOM > 0) LG = stage_lds_form(sc, lds_geom);
+}
+__device__ inline void flush_trav_counters(const DParams &R, const DQueues &Q, uint32_t nn, uint32_t nt, const StepCount &stepc) {
+    if (R.counters_on) { atomicAdd(&Q.stats[CNT_NODES], (unsigned long long)nn); atomicAdd(&Q.stats[CNT_TRIS], (unsigned long long)nt); atomicAdd(&Q.stats[CNT_NODE_STEPS], (unsigned long long)stepc.node_steps); atomicAdd(&Q.stats[CNT_NODE_VISITS], (unsigned long long)stepc.node_visits); atomicAdd(&Q.stats[CNT_TRI_STEPS], (unsigned long long)stepc.tri_steps); }
+}
 // One queue segment through the extension stage: the wave's refill loop, then (kinds_mask != 0) the segment's epilogue.  Called by
 // k_extend_rf for every segment the wave takes and by k_tail for its segment's remaining rounds.
 template <int FEAT, int DEPTH, bool OVF, int GEOM, bool VOTE>
@@ -616,9 +578,8 @@ __global__ __launch_bounds__(BLOCK, (TravWaves<FEAT, DEPTH, GEOM>::N)) void k_ex
     __shared__ unsigned long long lds_stack[DEPTH * BLOCK];
     __shared__ v4 lds_geom[TravLds<DEPTH, GEOM>::V4];
     if (round_is_dead(Q, it)) return;
-    LdsGeom LG; LG.root = LG.tri0 = LG.tri_copy = 0;
-    const GeomTop GG = stage_top(sc, lds_geom, TravLds<DEPTH, GEOM>::TOP);
-    if (GEOM > 0) LG = stage_lds_form(sc, lds_geom);
+    GeomTop GG; LdsGeom LG;
+    stage_geometry<DEPTH, GEOM>(sc, lds_geom, GG, LG);
     __syncthreads(); // the only barrier of the kernel: from here on the four waves of the workgroup are independent
     LdsStack<DEPTH, OVF> stk; stk.init(lds_stack, spill);
     uint32_t nn = 0, nt = 0; StepCount stepc;
@@ -630,7 +591,7 @@ __global__ __launch_bounds__(BLOCK, (TravWaves<FEAT, DEPTH, GEOM>::N)) void k_ex
 #else
     for (uint32_t s = seg_next(ticket, Gn); s < Gn; s = seg_next(ticket, Gn)) extend_segment<FEAT, DEPTH, OVF, GEOM, VOTE>(R, sc, P, Q, it, seg_cap, thresh, kinds_mask, Gn, s, GG, LG, stk, nn, nt, stepc);
 #endif
-    if (R.counters_on) { atomicAdd(&Q.stats[CNT_NODES], (unsigned long long)nn); atomicAdd(&Q.stats[CNT_TRIS], (unsigned long long)nt); atomicAdd(&Q.stats[CNT_NODE_STEPS], (unsigned long long)stepc.node_steps); atomicAdd(&Q.stats[CNT_NODE_VISITS], (unsigned long long)stepc.node_visits); atomicAdd(&Q.stats[CNT_TRI_STEPS], (unsigned long long)stepc.tri_steps); }
+    flush_trav_counters(R, Q, nn, nt, stepc);
 }
 
 // The two scene queries of a pending NEE record with lane refill: a lane walks the shadow ray (any hit), then the MIS
@@ -708,14 +669,13 @@ __global__ __launch_bounds__(BLOCK, (TravWaves<FEAT, DEPTH, GEOM>::N)) void k_co
     __shared__ unsigned long long lds_stack[DEPTH * BLOCK];
     __shared__ v4 lds_geom[TravLds<DEPTH, GEOM>::V4];
     if (round_is_dead(Q, it)) return;
-    LdsGeom LG; LG.root = LG.tri0 = LG.tri_copy = 0;
-    const GeomTop GG = stage_top(sc, lds_geom, TravLds<DEPTH, GEOM>::TOP);
-    if (GEOM > 0) LG = stage_lds_form(sc, lds_geom);
+    GeomTop GG; LdsGeom LG;
+    stage_geometry<DEPTH, GEOM>(sc, lds_geom, GG, LG);
     __syncthreads();
     LdsStack<DEPTH, OVF> stk; stk.init(lds_stack, spill);
     uint32_t nn = 0, nt = 0; StepCount stepc;
     for (uint32_t s = seg_next(ticket, Gn); s < Gn; s = seg_next(ticket, Gn)) connect_segment<FEAT, DEPTH, OVF, GEOM, VOTE>(sc, P, Q, it, seg_cap, thresh, fused_resolve, Gn, s, GG, LG, stk, nn, nt, stepc);
-    if (R.counters_on) { atomicAdd(&Q.stats[CNT_NODES], (unsigned long long)nn); atomicAdd(&Q.stats[CNT_TRIS], (unsigned long long)nt); atomicAdd(&Q.stats[CNT_NODE_STEPS], (unsigned long long)stepc.node_steps); atomicAdd(&Q.stats[CNT_NODE_VISITS], (unsigned long long)stepc.node_visits); atomicAdd(&Q.stats[CNT_TRI_STEPS], (unsigned long long)stepc.tri_steps); }
+    flush_trav_counters(R, Q, nn, nt, stepc);
 }
 
 // estimate_direct's use of the two answers (integrator.rs:66-78, 121-134) and `l += beta * nLights * ld`, full waves
@@ -1028,11 +988,14 @@ __global__ __launch_bounds__(BLOCK, (ShadeWaves<MAT, FEAT>::N)) void k_shade(DPa
 // the waves of a workgroup are in different rounds: draws read the global tables (sob_n = 0).
 // Instantiated for scenes of ONE material bucket whose traversal kernels are the lean ones (Cornell: Matte; colonnade: Disney +
 // image textures); two workgroups per CU (the Matte shade stage's registers, the LDS of both stages).
+// Its vote policy is compiled in, the launch policy's defaults: the extension stage votes, the connection stage for quad-form scenes only
+// (HipBackend::tail_fn hands a render with other votes no tail).
+constexpr bool tail_votes_connect(int geom) { return geom == 0; }
 template <int MAT, int FEAT, int GEOM, bool OVF, int DEPTH = 8>
 __global__ __launch_bounds__(BLOCK, 2) void k_tail(DParams R, DSampler S, DCamera C, DScene sc, StackSpill spill, DPaths P, DQueues Q, uint32_t it0, uint32_t it_end, uint32_t seg_cap, uint32_t thresh_e, uint32_t thresh_c,
                                                    uint32_t kinds_mask, ShadeLdsCfg cfg, uint32_t Gn, uint32_t *ticket) {
     constexpr int FEAT_T = FEAT_SIMPLE;
-    constexpr bool VOTE_C = GEOM == 0; // (the launch policy's defaults: phase voting in the connection stage for quad-form scenes only)
+    constexpr bool VOTE_C = tail_votes_connect(GEOM);
     __shared__ unsigned long long lds_stack[DEPTH * BLOCK];
     __shared__ v4 lds_geom[TravLds<DEPTH, GEOM>::V4];
     __shared__ v4 lds_pf[ShadeLdsSizes<FEAT, false>::NPF * BLOCK];
@@ -1042,9 +1005,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tail(DParams R, DSampler S, DCamer
     __shared__ float lds_marg[ShadeLdsSizes<FEAT, false>::MARG ? SH_MARG_WORDS : 1];
     static_assert(2u * lds_alloc((uint32_t)(sizeof(lds_stack) + sizeof(lds_geom) + sizeof(lds_pf) + sizeof(lds_sob) + sizeof(lds_tri) + sizeof(lds_light) + sizeof(lds_marg))) <= (uint32_t)PTRS_LDS_PER_CU, "two tail workgroups per CU");
     if (round_is_dead(Q, it0)) return;
-    LdsGeom LG; LG.root = LG.tri0 = LG.tri_copy = 0;
-    const GeomTop GG = stage_top(sc, lds_geom, TravLds<DEPTH, GEOM>::TOP);
-    if (GEOM > 0) LG = stage_lds_form(sc, lds_geom);
+    GeomTop GG; LdsGeom LG;
+    stage_geometry<DEPTH, GEOM>(sc, lds_geom, GG, LG);
     cfg.sob_n = 0;
     const ShadeCtxLds<false> X = stage_shade_tables<FEAT, false>(S, sc, cfg, lds_sob, lds_tri, lds_light, lds_marg);
     __syncthreads(); // the only barrier
@@ -1074,7 +1036,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tail(DParams R, DSampler S, DCamer
         }
     }
     if (err_dim) atomicOr(&Q.stats[CNT_ERR], (unsigned long long)PTRS_ERRFLAG_SOBOL_DIM);
-    if (R.counters_on) { atomicAdd(&Q.stats[CNT_NODES], (unsigned long long)nn); atomicAdd(&Q.stats[CNT_TRIS], (unsigned long long)nt); atomicAdd(&Q.stats[CNT_NODE_STEPS], (unsigned long long)stepc.node_steps); atomicAdd(&Q.stats[CNT_NODE_VISITS], (unsigned long long)stepc.node_visits); atomicAdd(&Q.stats[CNT_TRI_STEPS], (unsigned long long)stepc.tri_steps); }
+    flush_trav_counters(R, Q, nn, nt, stepc);
 }
 
 // The environment light's samples of a round's vertices, ahead of the round's shade kernels.  Which light a vertex samples and with
@@ -1144,6 +1106,32 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_counts(const uint32_t *__restr
     if (threadIdx.x == 0) totals[blockIdx.x] = acc;
 }
 
+// What the film gathers k_film and k_film_aov share (the accumulators and the LDS arrays are each kernel's own).  A thread's place: its tile's
+// first pixel, its pixel in the tile and on the film, whether that pixel exists, and its column and row as two bits of a footprint mask.
+struct FilmTile { int32_t tx0, ty0, lx, ly, x, y; bool live; uint32_t my_bits; };
+__device__ inline FilmTile film_tile(const DParams &R, int32_t y0, int32_t y1, int32_t tiles_x) {
+    const int32_t tx0 = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * 16, ty0 = y0 + (int32_t)(blockIdx.x / (uint32_t)tiles_x) * 16;
+    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
+    return FilmTile{tx0, ty0, lx, ly, tx0 + lx, ty0 + ly, tx0 + lx < R.W && ty0 + ly < y1, (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly))};
+}
+// Entry e of the tile's 20x20 apron for sample index k: the path slot of that sample, or false where the pass has none.
+__device__ inline bool film_apron_pid(const DParams &R, const DSampler &S, const FilmTile &T, uint32_t e, uint32_t k, uint32_t npix, uint32_t &pid) {
+    const int32_t sx = T.tx0 - 2 + (int32_t)(e % 20u) - S.min_x, sy = T.ty0 - 2 + (int32_t)(e / 20u) - S.min_y;
+    pid = k * npix + (uint32_t)(sy - R.row0) * (uint32_t)R.NX + (uint32_t)sx; // (only meaningful where the test below holds)
+    return sx >= 0 && sx < R.NX && sy >= R.row0 && sy < R.row1;
+}
+// The sample's footprint [p0x, p1x) x [p0y, p1y) (film.rs:66-73) against the tile, worked out ONCE per staged sample: bit c set when
+// the tile's column c is inside, bit 16 + r for row r.  A pixel's test is then `(mask & my two bits) == my two bits` -- two
+// instructions instead of film_weight's fourteen (four ceil / floor, four conversions, four comparisons ...) per (sample, pixel) pair.
+// (pdx, pdy) = p_film - 0.5: film_weight's own first steps on the same values.
+__device__ inline uint32_t film_footprint_mask(float pdx, float pdy, const FilmTile &T) {
+    const int32_t p0x = (int32_t)ceil_(pdx - 2.0f), p0y = (int32_t)ceil_(pdy - 2.0f), p1x = (int32_t)(floor_(pdx + 2.0f) + 1.0f), p1y = (int32_t)(floor_(pdy + 2.0f) + 1.0f);
+    auto span = [](int32_t lo, int32_t hi) { // bits [lo, hi) of a 16-bit field, both ends clipped to it
+        const uint32_t l = (uint32_t)(lo < 0 ? 0 : (lo > 16 ? 16 : lo)), h = (uint32_t)(hi < 0 ? 0 : (hi > 16 ? 16 : hi));
+        return h > l ? ((1u << h) - 1u) & ~((1u << l) - 1u) : 0u;
+    };
+    return span(p0x - T.tx0, p1x - T.tx0) | (span(p0y - T.ty0, p1y - T.ty0) << 16);
+}
 // Film gather, one workgroup per 16x16 tile of output pixels.  Per sample index the 20x20 neighbourhood of
 // sample-pixels (p_film and radiance) is staged in LDS once and read by the 256 pixels of the tile, instead
 // of every pixel fetching its 25 neighbours from HBM/L2 (16x less traffic; the first version of this kernel
@@ -1151,52 +1139,39 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_counts(const uint32_t *__restr
 __global__ __launch_bounds__(BLOCK) void k_film(DParams R, DSampler S, DPaths P, const float *__restrict__ table, v4 *film, int32_t y0, int32_t y1, int32_t tiles_x) {
     __shared__ float tab[256];
     __shared__ v4 s_a[400]; __shared__ float s_lb[400]; // p_film.xy - 0.5, L.rg | L.b: one 16-byte and one 4-byte LDS read per candidate that contributes
-    // The sample's footprint [p0x, p1x) x [p0y, p1y) (film.rs:66-73) against the tile, worked out ONCE per staged sample: bit c set when
-    // the tile's column c is inside, bit 16 + r for row r.  A pixel's test is then `(mask & my two bits) == my two bits` -- two
-    // instructions instead of film_weight's fourteen (four ceil / floor, four conversions, four comparisons ...) per (sample, pixel) pair.
-    __shared__ uint32_t s_m[400];
+    __shared__ uint32_t s_m[400];                       // footprint masks
     tab[threadIdx.x] = table[threadIdx.x];
-    const int32_t tx0 = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * 16, ty0 = y0 + (int32_t)(blockIdx.x / (uint32_t)tiles_x) * 16;
-    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
-    const int32_t x = tx0 + lx, y = ty0 + ly;
-    const bool live = x < R.W && y < y1;
-    const uint32_t my_bits = (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly));
+    const FilmTile T = film_tile(R, y0, y1, tiles_x);
     v4 acc; acc.x = acc.y = acc.z = acc.w = 0.0f;
-    if (live) acc = film[(size_t)y * (size_t)R.W + (size_t)x];
+    if (T.live) acc = film[(size_t)T.y * (size_t)R.W + (size_t)T.x];
     const uint32_t npix = (uint32_t)(R.row1 - R.row0) * (uint32_t)R.NX;
     const uint32_t ns = R.s1 - R.s0;
     for (uint32_t k = 0; k < ns; ++k) {
         __syncthreads(); // previous round's reads are done (and `tab` is visible on the first round)
         for (uint32_t e = threadIdx.x; e < 400u; e += BLOCK) {
-            const int32_t sx = tx0 - 2 + (int32_t)(e % 20u) - S.min_x, sy = ty0 - 2 + (int32_t)(e / 20u) - S.min_y;
             float pfx = -1.0e9f, pfy = -1.0e9f, lr = 0.0f, lg = 0.0f, lb = 0.0f; // far away: no pixel is in its footprint
-            if (sx >= 0 && sx < R.NX && sy >= R.row0 && sy < R.row1) {
-                const uint32_t pid = k * npix + (uint32_t)(sy - R.row0) * (uint32_t)R.NX + (uint32_t)sx;
+            uint32_t pid = 0;
+            if (film_apron_pid(R, S, T, e, k, npix, pid)) {
                 const f2a pf = pslot(P.pfilm, pid); const v4 Lv = pslot(P.L, pid);
                 pfx = pf.x; pfy = pf.y; lr = Lv.x; lg = Lv.y; lb = Lv.z;
             }
-            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f; // film_weight's own first steps on the same values
-            const int32_t p0x = (int32_t)ceil_(pdx - 2.0f), p0y = (int32_t)ceil_(pdy - 2.0f), p1x = (int32_t)(floor_(pdx + 2.0f) + 1.0f), p1y = (int32_t)(floor_(pdy + 2.0f) + 1.0f);
-            auto span = [](int32_t lo, int32_t hi) { // bits [lo, hi) of a 16-bit field, both ends clipped to it
-                const uint32_t l = (uint32_t)(lo < 0 ? 0 : (lo > 16 ? 16 : lo)), h = (uint32_t)(hi < 0 ? 0 : (hi > 16 ? 16 : hi));
-                return h > l ? ((1u << h) - 1u) & ~((1u << l) - 1u) : 0u;
-            };
-            s_m[e] = span(p0x - tx0, p1x - tx0) | (span(p0y - ty0, p1y - ty0) << 16);
+            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f;
+            s_m[e] = film_footprint_mask(pdx, pdy, T);
             v4 a; a.x = pdx; a.y = pdy; a.z = lr; a.w = lg; s_a[e] = a; s_lb[e] = lb;
         }
         __syncthreads();
-        if (live) {
+        if (T.live) {
             for (int32_t dx = 0; dx < 5; ++dx)
                 for (int32_t dy = 0; dy < 5; ++dy) {
-                    const int32_t e = (ly + dy) * 20 + (lx + dx);
-                    if ((s_m[e] & my_bits) != my_bits) continue; // x < p0x || x >= p1x || y < p0y || y >= p1y
+                    const int32_t e = (T.ly + dy) * 20 + (T.lx + dx);
+                    if ((s_m[e] & T.my_bits) != T.my_bits) continue; // x < p0x || x >= p1x || y < p0y || y >= p1y
                     const v4 a = s_a[e];
-                    const float w = film_weight_inside(a.x, a.y, x, y, tab);
+                    const float w = film_weight_inside(a.x, a.y, T.x, T.y, tab);
                     acc.x += a.z * w; acc.y += a.w * w; acc.z += s_lb[e] * w; acc.w += w;
                 }
         }
     }
-    if (live) film[(size_t)y * (size_t)R.W + (size_t)x] = acc;
+    if (T.live) film[(size_t)T.y * (size_t)R.W + (size_t)T.x] = acc;
 }
 
 // The stratified sampler's tables: one thread per 16x16 tile of the sample bounds, seeded with the tile's index like the
@@ -1211,7 +1186,7 @@ __global__ __launch_bounds__(64) void k_strat_tables(int32_t NX, int32_t NY, uin
 
 // The extension rays of round `it` as (o, d, +inf) records, whole 64-entry blocks of a segment together (the order a traversal wave meets them in)
 __global__ __launch_bounds__(BLOCK) void k_dump_rays(DPaths P, DQueues Q, uint32_t it, uint32_t seg_cap, uint32_t G, uint32_t max_rays, float *out, uint32_t *n_out) {
-    const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, s = wave_of_launch();
     if (s >= G) return;
     const uint32_t e0 = s * seg_cap, par = it & 1u;
     const uint32_t n = *seg_count(Q, it, Q_EXT, G, s);
@@ -1243,7 +1218,7 @@ __global__ __launch_bounds__(BLOCK) void k_export_samples(DParams R, DSampler S,
 // like epilogue_wave: path slots and hits of 64 consecutive positions are two coalesced reads; the values go to the path's slot.
 template <int FEAT>
 __global__ __launch_bounds__(BLOCK) void k_aov(DParams R, DCamera C, DScene sc, DPaths P, DQueues Q, DAov A, uint32_t off, uint32_t seg_cap, uint32_t G) { // off: the pass's first slot in A's arrays
-    const uint32_t lane = threadIdx.x & 63u, s = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, s = wave_of_launch();
     if (s >= G) return;
     const uint32_t e0 = s * seg_cap;
     const uint32_t n = rfl(*seg_count(Q, 0, Q_EXT, G, s));
@@ -1272,16 +1247,12 @@ __global__ __launch_bounds__(BLOCK) void k_film_aov(DParams R, DSampler S, DPath
     __shared__ v4 s_p[400], s_al[400], s_n[400]; // p_film.xy - 0.5, depth, coverage | albedo.rgb | normal.rgb
     __shared__ uint32_t s_m[400];                // footprint masks (k_film)
     tab[threadIdx.x] = table[threadIdx.x];
-    const int32_t tx0 = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * 16, ty0 = y0 + (int32_t)(blockIdx.x / (uint32_t)tiles_x) * 16;
-    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
-    const int32_t x = tx0 + lx, y = ty0 + ly;
-    const bool live = x < R.W && y < y1;
-    const uint32_t my_bits = (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly));
+    const FilmTile T = film_tile(R, y0, y1, tiles_x);
     const bool want_al = F.plane[AOV_ALBEDO] != nullptr, want_n = F.plane[AOV_NORMAL] != nullptr, want_d = F.plane[AOV_DEPTH] != nullptr;
-    const size_t px = (size_t)y * (size_t)R.W + (size_t)x;
+    const size_t px = (size_t)T.y * (size_t)R.W + (size_t)T.x;
     v4 acc_al, acc_n, acc_d;
     acc_al.x = acc_al.y = acc_al.z = acc_al.w = 0.0f; acc_n = acc_al; acc_d = acc_al;
-    if (live) {
+    if (T.live) {
         if (want_al) acc_al = F.plane[AOV_ALBEDO][px];
         if (want_n) acc_n = F.plane[AOV_NORMAL][px];
         if (want_d) acc_d = F.plane[AOV_DEPTH][px];
@@ -1291,38 +1262,32 @@ __global__ __launch_bounds__(BLOCK) void k_film_aov(DParams R, DSampler S, DPath
     for (uint32_t k = 0; k < ns; ++k) {
         __syncthreads(); // previous round's reads are done (and `tab` is visible on the first round)
         for (uint32_t e = threadIdx.x; e < 400u; e += BLOCK) {
-            const int32_t sx = tx0 - 2 + (int32_t)(e % 20u) - S.min_x, sy = ty0 - 2 + (int32_t)(e / 20u) - S.min_y;
             float pfx = -1.0e9f, pfy = -1.0e9f; // far away: no pixel is in its footprint
             v4 al, nd; al.x = al.y = al.z = al.w = 0.0f; nd = al;
-            if (sx >= 0 && sx < R.NX && sy >= R.row0 && sy < R.row1) {
-                const uint32_t pid = k * npix + (uint32_t)(sy - R.row0) * (uint32_t)R.NX + (uint32_t)sx;
+            uint32_t pid = 0;
+            if (film_apron_pid(R, S, T, e, k, npix, pid)) {
                 const f2a pf = pslot(P.pfilm, pid);
                 pfx = pf.x; pfy = pf.y; al = pslot(A.albedo, pid); nd = pslot(A.normal, pid);
             }
-            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f; // film_weight's own first steps on the same values
-            const int32_t p0x = (int32_t)ceil_(pdx - 2.0f), p0y = (int32_t)ceil_(pdy - 2.0f), p1x = (int32_t)(floor_(pdx + 2.0f) + 1.0f), p1y = (int32_t)(floor_(pdy + 2.0f) + 1.0f);
-            auto span = [](int32_t lo, int32_t hi) { // bits [lo, hi) of a 16-bit field, both ends clipped to it
-                const uint32_t l = (uint32_t)(lo < 0 ? 0 : (lo > 16 ? 16 : lo)), h = (uint32_t)(hi < 0 ? 0 : (hi > 16 ? 16 : hi));
-                return h > l ? ((1u << h) - 1u) & ~((1u << l) - 1u) : 0u;
-            };
-            s_m[e] = span(p0x - tx0, p1x - tx0) | (span(p0y - ty0, p1y - ty0) << 16);
+            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f;
+            s_m[e] = film_footprint_mask(pdx, pdy, T);
             v4 a; a.x = pdx; a.y = pdy; a.z = nd.w; a.w = al.w; s_p[e] = a; s_al[e] = al; s_n[e] = nd;
         }
         __syncthreads();
-        if (live) {
+        if (T.live) {
             for (int32_t dx = 0; dx < 5; ++dx)
                 for (int32_t dy = 0; dy < 5; ++dy) {
-                    const int32_t e = (ly + dy) * 20 + (lx + dx);
-                    if ((s_m[e] & my_bits) != my_bits) continue; // x < p0x || x >= p1x || y < p0y || y >= p1y
+                    const int32_t e = (T.ly + dy) * 20 + (T.lx + dx);
+                    if ((s_m[e] & T.my_bits) != T.my_bits) continue; // x < p0x || x >= p1x || y < p0y || y >= p1y
                     const v4 a = s_p[e];
-                    const float w = film_weight_inside(a.x, a.y, x, y, tab);
+                    const float w = film_weight_inside(a.x, a.y, T.x, T.y, tab);
                     if (want_al) { const v4 c = s_al[e]; acc_al.x += c.x * w; acc_al.y += c.y * w; acc_al.z += c.z * w; acc_al.w += w; }
                     if (want_n) { const v4 c = s_n[e]; acc_n.x += c.x * w; acc_n.y += c.y * w; acc_n.z += c.z * w; acc_n.w += w; }
                     if (want_d) { acc_d.x += a.z * w; acc_d.y += a.w * w; acc_d.z += 0.0f * w; acc_d.w += w; }
                 }
         }
     }
-    if (live) {
+    if (T.live) {
         if (want_al) F.plane[AOV_ALBEDO][px] = acc_al;
         if (want_n) F.plane[AOV_NORMAL][px] = acc_n;
         if (want_d) F.plane[AOV_DEPTH][px] = acc_d;
@@ -1342,207 +1307,7 @@ __global__ __launch_bounds__(BLOCK) void k_export_aov(DParams R, DSampler S, DAo
     }
 }
 
-// ---- denoiser (pt_denoise.h): prepare, `iterations` a-trous launches over ping / pong, finish ------------------------------------
-// No queues, no atomics, nothing to spin on: one thread per pixel, every tap bounds-checked.  The iteration kernel has two forms over
-// the same per-pixel function (dn_atrous), which differ in where a tap comes from:
-//   k_dn_iter        a workgroup is 64 x 4 pixels, lanes are neighbours in x, every tap is two 16-byte global loads
-//   k_dn_iter_lds<S> for step S the rows y = r (mod S) form an image of their own with unit row step: a workgroup stages 64 + 4 S
-//                    contiguous columns x DN_TILE_T + 4 lattice rows of colour and guide in LDS and filters 64 x DN_TILE_T outputs
-//                    out of it; pixels beyond the image are staged as empty ones.  (64 + 4 S)(T + 4) 32 B: 17 KiB at S = 1, 48 KiB at
-//                    S = 16, the largest step instantiated -- beyond it the tile would not leave room for several workgroups on a CU.
-enum : int { DN_TILE_W = 64, DN_TILE_T = 8, DN_LDS_MAX_STEP = 16 };
-enum : uint32_t { DN_LDS_DEFAULT_STEPS = 0u }; // option denoise_lds = -1: the steps (a bit mask) whose shipped form is the LDS tile (the measurement)
-
-__global__ __launch_bounds__(BLOCK) void k_dn_prepare(uint32_t n, const v4 *__restrict__ B, const v4 *__restrict__ A, const v4 *__restrict__ N, const v4 *__restrict__ D,
-                                                      v4 *__restrict__ x, v4 *__restrict__ g, v4 *__restrict__ a, int demodulate) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const DnPixel o = dn_prepare(B[i], A[i], N[i], D[i], demodulate != 0);
-    x[i] = o.x; g[i] = o.g; a[i] = o.a;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_dn_iter(DnIter it, const v4 *__restrict__ xin, const v4 *__restrict__ gin, v4 *__restrict__ xout) {
-    const int32_t px = (int32_t)blockIdx.x * 64 + (int32_t)(threadIdx.x & 63u), py = (int32_t)blockIdx.y * WAVES + (int32_t)(threadIdx.x >> 6);
-    if (px >= it.W || py >= it.H) return;
-    const uint32_t p = (uint32_t)py * (uint32_t)it.W + (uint32_t)px;
-    auto fetch = [&](int dx, int dy, v4 &xq, v4 &gq) -> bool {
-        const int32_t qx = px + it.step * dx, qy = py + it.step * dy;
-        if (qx < 0 || qx >= it.W || qy < 0 || qy >= it.H) return false;
-        const uint32_t q = (uint32_t)qy * (uint32_t)it.W + (uint32_t)qx;
-        xq = xin[q]; gq = gin[q];
-        return dn_ok(xq);
-    };
-    xout[p] = dn_atrous(it, xin[p], gin[p], fetch);
-}
-
-template <int S>
-__global__ __launch_bounds__(BLOCK) void k_dn_iter_lds(DnIter it, const v4 *__restrict__ xin, const v4 *__restrict__ gin, v4 *__restrict__ xout) {
-    constexpr int COLS = DN_TILE_W + 4 * S, ROWS = DN_TILE_T + 4;
-    __shared__ v4 sx[ROWS * COLS], sg[ROWS * COLS];
-    const int32_t r = (int32_t)blockIdx.z, x0 = (int32_t)blockIdx.x * DN_TILE_W, j0 = (int32_t)blockIdx.y * DN_TILE_T; // residue, first column, first lattice row
-    if (r + S * j0 >= it.H) return; // (the whole workgroup: no output row)
-    for (int idx = (int)threadIdx.x; idx < ROWS * COLS; idx += BLOCK) {
-        const int row = idx / COLS, col = idx - row * COLS;
-        const int32_t gx = x0 - 2 * S + col, gy = r + S * (j0 - 2 + row);
-        v4 xv = mkv4(splat3(0.0f), dn_empty_mark()), gv = mkv4(splat3(0.0f), 0.0f);
-        if (gx >= 0 && gx < it.W && gy >= 0 && gy < it.H) { const uint32_t q = (uint32_t)gy * (uint32_t)it.W + (uint32_t)gx; xv = xin[q]; gv = gin[q]; }
-        sx[idx] = xv; sg[idx] = gv;
-    }
-    __syncthreads();
-    const int lx = (int)(threadIdx.x & 63u);
-    const int32_t px = x0 + lx;
-    for (int k = (int)(threadIdx.x >> 6); k < DN_TILE_T; k += WAVES) {
-        const int32_t py = r + S * (j0 + k);
-        if (px >= it.W || py >= it.H) continue;
-        const int c = (k + 2) * COLS + lx + 2 * S;
-        auto fetch = [&](int dx, int dy, v4 &xq, v4 &gq) -> bool { const int q = c + dy * COLS + dx * S; xq = sx[q]; gq = sg[q]; return dn_ok(xq); };
-        xout[(uint32_t)py * (uint32_t)it.W + (uint32_t)px] = dn_atrous(it, sx[c], sg[c], fetch);
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_dn_finish(uint32_t n, const v4 *__restrict__ x, const v4 *__restrict__ a, v4 *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = dn_finish(x[i], a[i]);
-}
-
-// ---- the film's error against its half film (pt_converge.h) ----------------------------------------------------------
-// One workgroup per 16 x 16 tile, one thread per pixel: 32 bytes read per pixel, 8 written per tile.  The 256 errors are summed by the
-// stride-halving tree of cv_tile_sum: strides 128 and 64 through LDS, the last six across the lanes of wave 0 (lane i takes lane
-// i + off's value: for i < off that is v[i] += v[i + off]; what the lanes beyond off make of it is never read again).  The valid
-// counts ride along as integers.  A pixel beyond the image is an empty slot and is never loaded.
-__global__ __launch_bounds__(BLOCK) void k_film_error(int32_t W, int32_t H, int32_t tiles_x, const v4 *__restrict__ film, const v4 *__restrict__ half, PtrsTileError *__restrict__ tiles) {
-    static_assert(BLOCK == CV_SLOTS, "one thread per slot of a tile");
-    __shared__ float v[CV_SLOTS]; __shared__ uint32_t c[CV_SLOTS];
-    const uint32_t t = threadIdx.x;
-    const int32_t x = (int32_t)(blockIdx.x % (uint32_t)tiles_x) * CV_TILE + (int32_t)(t & 15u), y = (int32_t)(blockIdx.x / (uint32_t)tiles_x) * CV_TILE + (int32_t)(t >> 4);
-    CvPixel p; p.e = 0.0f; p.valid = 0u;
-    if (x < W && y < H) { const size_t q = (size_t)y * (size_t)W + (size_t)x; p = cv_pixel(film[q], half[q]); }
-    v[t] = p.e; c[t] = p.valid;
-    __syncthreads();
-    if (t < 128u) { v[t] = v[t] + v[t + 128u]; c[t] += c[t + 128u]; }
-    __syncthreads();
-    if (t < 64u) {
-        float e = v[t] + v[t + 64u]; uint32_t n = c[t] + c[t + 64u];
-        for (int off = 32; off > 0; off >>= 1) { e = e + __shfl_down(e, off); n += (uint32_t)__shfl_down((int)n, off); }
-        if (t == 0u) tiles[blockIdx.x] = cv_tile(e, n);
-    }
-}
-
-// The tile records -> the summary, one workgroup: every thread keeps the best of its tiles (cv_better: larger error, then lower index)
-// and their valid pixels, then a tree over the 256 candidates.  Maximum and integer sum do not depend on the order.
-__global__ __launch_bounds__(BLOCK) void k_film_error_summary(const PtrsTileError *__restrict__ tiles, uint32_t n_tiles, uint32_t tiles_x, uint32_t tiles_y, PtrsFilmErrorSummary *__restrict__ out) {
-    __shared__ float se[BLOCK]; __shared__ uint32_t si[BLOCK]; __shared__ unsigned long long sn[BLOCK];
-    const uint32_t t = threadIdx.x;
-    float e = -1.0f; uint32_t idx = 0xffffffffu; unsigned long long n = 0ull; // (any tile beats the start: tile errors are >= 0)
-    for (uint32_t i = t; i < n_tiles; i += BLOCK) {
-        const PtrsTileError T = tiles[i];
-        if (cv_better(T.error, i, e, idx)) { e = T.error; idx = i; }
-        n += T.valid;
-    }
-    se[t] = e; si[t] = idx; sn[t] = n;
-    for (uint32_t off = BLOCK / 2u; off > 0u; off >>= 1) {
-        __syncthreads();
-        if (t < off) {
-            if (cv_better(se[t + off], si[t + off], se[t], si[t])) { se[t] = se[t + off]; si[t] = si[t + off]; }
-            sn[t] += sn[t + off];
-        }
-    }
-    if (t == 0u) { PtrsFilmErrorSummary s; s.max_tile_error = se[0]; s.worst_tile = si[0]; s.valid_pixels = sn[0]; s.tiles_x = tiles_x; s.tiles_y = tiles_y; *out = s; }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t idx = sobol_index(S, sn[i], (uint32_t)(px[i] - S.min_x), (uint32_t)(py[i] - S.min_y));
-    if (idx_out) idx_out[i] = idx;
-    out[i] = sample_dimension(S, idx, dims[i], pixel_scramble(px[i], py[i]), px[i], py[i]);
-}
-
-// Self-test of the shared-divisor division (pt_vec.h, div_shared3) against the compiler's IEEE division, bit for bit, on
-// operand sets drawn from a counter-based generator.  mode 0: raw random bit patterns (every class at its natural share: 1/256 each of
-// zeros + denormals and infinities + NaNs); 1: exponents around every threshold of the fast path's window and of v_div_scale /
-// v_div_fixup, mantissas random / all zeros / all ones, signed zeros; 2: the ranges of a render (pdf-like divisors 2^-27 .. 2^13,
-// radiance-like numerators, a quarter of them zero); 3: beta / (1 - q) of the Russian roulette; 4: quotients next to 1 and next to
-// rounding ties (a = b x small factors, a = b +- ulps).
-__device__ inline uint64_t mix64(uint64_t z) { z += 0x9e3779b97f4a7c15ull; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
-__device__ inline uint32_t edge_bits(uint32_t r) { // r: 32 random bits
-    const uint32_t exps[32] = {0, 0, 1, 2, 22, 23, 24, 25, 31, 32, 33, 78, 79, 80, 81, 82, 126, 127, 128, 150, 172, 173, 174, 175, 176, 221, 222, 223, 252, 253, 254, 255};
-    const uint32_t e = exps[r & 31u], how = (r >> 5) & 3u, sign = (r >> 7) & 1u;
-    const uint32_t man = how == 0u ? 0u : (how == 1u ? 0x7fffffu : ((r >> 9) & 0x7fffffu));
-    return (sign << 31) | (e << 23) | man;
-}
-__global__ __launch_bounds__(BLOCK) void k_selftest_div3(uint64_t seed, uint32_t mode, uint64_t per_thread, unsigned long long *out /* [0] mismatches, [1] fast-path sets */, uint32_t *first_bad /* 10 words + a lock */) {
-    const uint64_t tid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    unsigned long long bad = 0, fast = 0;
-    for (uint64_t k = 0; k < per_thread; ++k) {
-        const uint64_t h0 = mix64(seed ^ (tid * per_thread + k) * 0xd1342543de82ef95ull), h1 = mix64(h0);
-        uint32_t w[4] = {(uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32)};
-        if (mode == 1u) { for (int j = 0; j < 4; ++j) w[j] = edge_bits(w[j]); }
-        else if (mode == 2u) {
-            w[3] = ((100u + (w[3] >> 24) % 41u) << 23) | (w[3] & 0x7fffffu);
-            for (int j = 0; j < 3; ++j) w[j] = (w[j] >> 30) == 0u ? (w[j] & 0x80000000u) : (((90u + (w[j] >> 24) % 51u) << 23) | (w[j] & 0x7fffffu) | ((w[j] >> 29) == 7u ? 0x80000000u : 0u));
-        } else if (mode == 3u) {
-            const float mx = (float)(w[3] >> 8) * 0x1p-24f;
-            const float q = max_nz(0.05f, 1.0f - mx);
-            w[3] = f2u(1.0f - q);
-            for (int j = 0; j < 3; ++j) w[j] = f2u((float)(w[j] >> 8) * 0x1p-23f * ((w[j] & 255u) == 0u ? 0.0f : 1.0f));
-        } else if (mode == 4u) {
-            const uint32_t b = ((80u + (w[3] >> 24) % 90u) << 23) | (w[3] & 0x7fffffu) | ((w[3] >> 23 & 1u) << 31);
-            w[3] = b;
-            for (int j = 0; j < 3; ++j) {
-                const uint32_t sel = w[j] & 7u, d = (w[j] >> 3) & 15u;
-                const float fb = u2f(b);
-                float a = fb;
-                if (sel == 0u) a = u2f(b + d); else if (sel == 1u) a = u2f(b - d); else if (sel == 2u) a = fb * (float)(1u + d); else if (sel == 3u) a = fb * (1.0f + (float)d * 0x1p-23f);
-                else if (sel == 4u) a = fb * 0x1.fffffep-1f; else if (sel == 5u) a = fb * 0.5f + u2f((f2u(fb) & 0xff800000u) - (12u << 23)); else if (sel == 6u) a = u2f((b & 0xff800000u) | 0x7fffffu); else a = u2f(b & 0xff800000u);
-                w[j] = f2u(a);
-            }
-        }
-        const float ax = u2f(w[0]), ay = u2f(w[1]), az = u2f(w[2]), b = u2f(w[3]);
-        const f3 got = div_shared3(mk3(ax, ay, az), b);
-        const float wx = ax / b, wy = ay / b, wz = az / b; // the compiler's IEEE division
-        { // (how many sets took the fast path: the test wants to know that it was exercised)
-            const uint32_t LO = 80u << 23, HI = 175u << 23, ux = w[0] & 0x7fffffffu, uy = w[1] & 0x7fffffffu, uz = w[2] & 0x7fffffffu, us = w[3] & 0x7fffffffu;
-            auto okn = [&](uint32_t u) { return u == 0u || (u >= LO && u < HI); };
-            if (us >= LO && us < HI && okn(ux) && okn(uy) && okn(uz)) ++fast;
-        }
-        if (f2u(got.x) != f2u(wx) || f2u(got.y) != f2u(wy) || f2u(got.z) != f2u(wz)) {
-            ++bad;
-            if (atomicCAS(first_bad + 10, 0u, 1u) == 0u) { first_bad[0] = w[0]; first_bad[1] = w[1]; first_bad[2] = w[2]; first_bad[3] = w[3]; first_bad[4] = f2u(got.x); first_bad[5] = f2u(got.y); first_bad[6] = f2u(got.z); first_bad[7] = f2u(wx); first_bad[8] = f2u(wy); first_bad[9] = f2u(wz); }
-        }
-    }
-    if (bad) atomicAdd(out, bad);
-    atomicAdd(out + 1, fast);
-}
-
-// Known-answer probes (csrc/pt_probe.h): one row per thread, the same functions the host twin runs.
-struct ProbeArgs { float v[9]; }; // BSDF: ng, ns, dpdu; light: p, n (6 used)
-__global__ __launch_bounds__(BLOCK) void k_probe_bsdf(DScene sc, int32_t mat, int32_t kind, ProbeArgs frame, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    bsdf_probe_row(sc, mat, kind, frame.v, in + (uint64_t)i * PROBE_BSDF_IN, out + (uint64_t)i * PROBE_BSDF_OUT);
-}
-__global__ __launch_bounds__(BLOCK) void k_probe_light(DScene sc, int32_t light, ProbeArgs ref, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    light_probe_row(sc, light, ref.v, in + (uint64_t)i * PROBE_LIGHT_IN, out + (uint64_t)i * PROBE_LIGHT_OUT);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_probe_texture(DScene sc, int32_t tex, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    texture_probe_row(sc, tex, in + (uint64_t)i * PROBE_TEX_IN, out + (uint64_t)i * PROBE_TEX_OUT);
-}
-__global__ __launch_bounds__(BLOCK) void k_probe_surface(DScene sc, uint32_t prim, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    surface_probe_row(sc, prim, in + (uint64_t)i * PROBE_SURF_IN, out + (uint64_t)i * PROBE_SURF_OUT);
-}
-__global__ __launch_bounds__(BLOCK) void k_probe_math(uint32_t op, uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    math_probe_row(op, in + (uint64_t)i * PROBE_MATH_IN, out + (uint64_t)i * PROBE_MATH_OUT);
-}
+#include "pt_hip_post.h"
 
 // ---- device buffers ---------------------------------------------------------------------------------
 // Owns its block: the destructor frees it, so a scene, a denoiser or an entry point's locals need no release list and an early return
@@ -1712,12 +1477,44 @@ int require_spill(const PtrsScene *ps) {
     return PTRS_ERR_DEVICE;
 }
 
+// The template kernels in the order the code object lists them: the order in which they are first named, which is here.  The order is
+// measured (classroom's shade kernels ran 0.8 % slower with the extension kernels ahead of them): keep it when a kernel is added.
+#define PTRS_K(...) (const void *)__VA_ARGS__
+#define PTRS_TRAV_V(K, F, D, O, G) PTRS_K(K<F, D, O, G, true>), PTRS_K(K<F, D, O, G, false>)
+#define PTRS_TRAV_O(K, F, D, G) PTRS_TRAV_V(K, F, D, true, G), PTRS_TRAV_V(K, F, D, false, G)
+#define PTRS_TRAV_ALL(K, F) PTRS_TRAV_V(K, F, 9, false, LDS9_V4), PTRS_TRAV_O(K, F, 8, 640), PTRS_TRAV_O(K, F, 8, 1536), PTRS_TRAV_O(K, F, 8, 0), PTRS_TRAV_O(K, F, 16, 0)
+#define PTRS_CONNECT_ALL(F) PTRS_TRAV_ALL(k_connect_rf, F), PTRS_K(k_resolve<F>)
+#define PTRS_SHADE_ALL(F, E) PTRS_K(k_shade<0, F, E>), PTRS_K(k_shade<1, F, E>), PTRS_K(k_shade<2, F, E>), PTRS_K(k_shade<3, F, E>), PTRS_K(k_shade<4, F, E>), PTRS_K(k_shade<5, F, E>)
+#define PTRS_TAIL_O(M, F, G) PTRS_K(k_tail<M, F, G, true>), PTRS_K(k_tail<M, F, G, false>)
+[[maybe_unused]] const void *const k_code_object_order[] = {
+    PTRS_K(k_epilogue<FEAT_FULL>), PTRS_K(k_epilogue<FEAT_IMG_ENV>), PTRS_K(k_epilogue<FEAT_SIMPLE>), PTRS_CONNECT_ALL(FEAT_FULL), PTRS_CONNECT_ALL(FEAT_IMG_ENV), PTRS_CONNECT_ALL(FEAT_SIMPLE),
+    PTRS_SHADE_ALL(FEAT_SIMPLE, false), PTRS_SHADE_ALL(FEAT_IMG, false), PTRS_SHADE_ALL(FEAT_IMG_ENV, true), PTRS_SHADE_ALL(FEAT_IMG_ENV, false), PTRS_SHADE_ALL(FEAT_FULL, true), PTRS_SHADE_ALL(FEAT_FULL, false),
+    PTRS_K(k_env_presample<FEAT_IMG_ENV>), PTRS_K(k_env_presample<FEAT_FULL>), PTRS_K(k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, LDS9_V4, false, 9>), PTRS_TAIL_O(PTRS_MAT_MATTE, FEAT_SIMPLE, 640), PTRS_TAIL_O(PTRS_MAT_MATTE, FEAT_SIMPLE, 1536),
+    PTRS_TAIL_O(PTRS_MAT_MATTE, FEAT_SIMPLE, 0), PTRS_TAIL_O(PTRS_MAT_DISNEY, FEAT_IMG, 0), PTRS_K(k_aov<FEAT_SIMPLE>), PTRS_K(k_aov<FEAT_FULL>),
+    PTRS_K(k_dn_iter_lds<1>), PTRS_K(k_dn_iter_lds<2>), PTRS_K(k_dn_iter_lds<4>), PTRS_K(k_dn_iter_lds<8>), PTRS_K(k_dn_iter_lds<16>),
+    PTRS_K(k_trace<true, 8, false>), PTRS_K(k_trace<true, 8, true>), PTRS_K(k_trace<true, 16, false>), PTRS_K(k_trace<true, 16, true>), PTRS_K(k_trace<false, 8, false>), PTRS_K(k_trace<false, 8, true>), PTRS_K(k_trace<false, 16, false>), PTRS_K(k_trace<false, 16, true>),
+    PTRS_TRAV_ALL(k_extend_rf, FEAT_FULL), PTRS_TRAV_ALL(k_extend_rf, FEAT_IMG_ENV), PTRS_TRAV_ALL(k_extend_rf, FEAT_SIMPLE)};
+#undef PTRS_K
+#undef PTRS_TRAV_V
+#undef PTRS_TRAV_O
+#undef PTRS_TRAV_ALL
+#undef PTRS_CONNECT_ALL
+#undef PTRS_SHADE_ALL
+#undef PTRS_TAIL_O
+
 struct HipBackend {
     PtrsScene *ps; hipStream_t stream; SobolDevice *sob;
     DScene sc; DSampler S; DCamera C; DParams R; DPaths P; DQueues Q;
     uint32_t cap = 0, rows = 0, depth = 0, flags = 0, kinds_mask = 0;
     int feat = FEAT_FULL, feat_trace = FEAT_FULL;
-    uint32_t geom4 = 0xffffffffu; // 16-byte vectors needed to hold nodes + triangles in LDS
+    // Which traversal form this scene runs -- the template arguments of its kernels -- worked out ONCE (traversal_policy) and read by every
+    // pick of an instantiation, by tail_fn() and by the statistics.
+    struct TravForm {
+        int depth = 16, geom = 0; // LDS stack entries per lane (9, 8 or 16) and GEOM, the LDS staging area in 16-byte vectors: LDS9_V4 (depth 9), 640 or 1536 (depth 8), 0 = quad form out of global memory
+        bool ovf = false;         // the tree is deeper than the column: the excess spills to the global columns
+        uint32_t v4 = 0;          // the vectors this scene's LDS form takes (0: quad form)
+        bool vote = true, vote_connect = true; // phase voting in the extension / the connection kernel
+    } form;
     uint32_t G = 1, seg_cap = 0;  // segmented queues of the current pass
     // pipeline lanes: the members above (stream, R, P, Q, G, seg_cap) are those of the selected lane
     struct Lane { hipStream_t stream; DParams R; DPaths P; DQueues Q; uint32_t G, seg_cap; };
@@ -1780,7 +1577,6 @@ struct HipBackend {
     int share = 1;
     int grid_max = 8192;
     uint32_t refill_connect = 16;
-    bool vote = true, vote_connect = true;
     uint32_t refill = 16; // idle-lane threshold of the lane-refill kernels (64: a wave takes new rays only when all its lanes are idle)
     int rc = PTRS_OK;
     // timing
@@ -1843,7 +1639,7 @@ struct HipBackend {
     // one only partly filled: at G / W = 2.67 a third of the waves idle for the last third of every kernel (utilisation G / W / ceil(G / W) =
     // 0.89; the same at 5.33), at a whole ratio none do.
     uint32_t whole_rounds(uint32_t target) {
-        const uint32_t we = resident_grid(pick_extend(feat_trace, vote, ps->spill.p != nullptr)) * WAVES;
+        const uint32_t we = resident_grid(pick_extend()) * WAVES;
         uint32_t ws = 0;
         for (int k = 0; k < 6 && !ws; ++k) if (ps->H.kinds_present[k]) ws = resident_grid(shade_fn(k)) * WAVES;
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
@@ -1854,20 +1650,23 @@ struct HipBackend {
     }
     uint32_t *ticket(uint32_t it, int which) { return Q.tickets + ((size_t)it * Q_STRIDE + (size_t)which) * TK_LAUNCH_WORDS; }
 
-    // How the traversal kernels of this scene run: phase voting, idle-lane thresholds, geometry source.  begin() and ptrs_trace_bench both
-    // ask here, so the bench launches the kernel a frame launches.
+    // How the traversal kernels of this scene run: the form (stack column, geometry source, phase voting) and the idle-lane thresholds.
+    // begin() and ptrs_trace_bench both ask here, so the bench launches the kernel a frame launches.
     void traversal_policy(int feat_trace_) {
         feat_trace = feat_trace_;
+        const bool pair = ps->sc.n_nodes4 == 0; // pair form: fits the LDS staging area by construction (pt_host_scene.h); quad form: the global kernels
+        form.depth = (int)ps->stack_lds; form.ovf = ps->spill_lane_elems != 0; // (require_spill: nothing is launched for a deeper tree without its columns)
+        form.v4 = pair ? LN_V4 * ps->sc.n_nodes2 + 9u * ps->sc.n_prims : 0u;
+        form.geom = form.depth == 9 ? LDS9_V4 : (form.depth == 8 && pair && form.v4 <= 640u) ? 640 : (form.depth == 8 && pair && form.v4 <= 1536u) ? 1536 : 0;
         // phase voting: quad-node scenes gain in both traversal kernels; on the LDS pair form a step is cheap enough that the vote's
         // own instructions eat the gain in the connect kernel (+20 %), the extension kernel keeps 4 % (A/B on MI355X)
-        vote = opt.vote >= 0 ? opt.vote != 0 : true;
-        vote_connect = opt.vote >= 0 ? opt.vote == 1 : ps->sc.n_nodes4 != 0;
+        const bool vote = form.vote = opt.vote >= 0 ? opt.vote != 0 : true;
+        const bool vote_connect = form.vote_connect = opt.vote >= 0 ? opt.vote == 1 : !pair;
         // idle-lane threshold: a voting wave comes back for retire / refill in batches, and with the cheap steps of the kernels without
         // alpha masks a bigger batch pays (Cornell extend 88.8 -> 85.7 ms, colonnade connect 38.2 -> 36.4 ms at 32); the full-feature
         // kernels (classroom) are better off at 16 (extend 227 vs 233 ms).  0 = no refill while a lane still works (threshold 64).
         refill = (uint32_t)(opt.refill > 0 ? opt.refill : (opt.refill == 0 ? 64 : ((vote && feat_trace == FEAT_SIMPLE) ? 32 : 16)));
         refill_connect = (uint32_t)(opt.refill_connect > 0 ? opt.refill_connect : (opt.refill_connect == 0 ? 64 : ((vote_connect && feat_trace == FEAT_SIMPLE) ? 32 : 16)));
-        geom4 = ps->sc.n_nodes4 ? 0xffffffffu : LN_V4 * ps->sc.n_nodes2 + 9u * ps->sc.n_prims; // quad form: global kernels; pair form: fits the LDS staging area by construction (pt_host_scene.h)
     }
     int begin(const DScene &sc_, const DSampler &S_, const DCamera &C_, uint32_t capacity, uint32_t count_rows, uint32_t bvh_depth, uint32_t flags_, int feat_, int feat_trace_, std::string &err) {
         sc = sc_; S = S_; C = C_; cap = capacity; rows = count_rows; depth = bvh_depth; flags = flags_; feat = feat_;
@@ -1939,34 +1738,33 @@ struct HipBackend {
     void generate() { t0(T_AUX); hipLaunchKernelGGL(k_generate, dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, S, C, P, Q, seg_cap, G, (uint32_t)deal_by_region()); t1(); }
     int deal_by_region() const { return opt.deal; } // (option `deal`: measured slower, off)
 
-    // the instantiation of a traversal kernel for this scene: LDS stack depth, spill columns, geometry source, phase voting
+    // the instantiation of a traversal kernel for this scene's form (`v`: the kernel's own vote, form.vote or form.vote_connect)
     typedef void (*TravFn)(DParams, DScene, StackSpill, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *);
 #define PTRS_PICK(K, D, O, GE) (v ? (TravFn)K<FEAT, D, O, GE, true> : (TravFn)K<FEAT, D, O, GE, false>)
-#define PTRS_PICK_ALL(K) (ps->stack_lds == 9 ? PTRS_PICK(K, 9, false, LDS9_V4) : ps->stack_lds == 8 ? (geom4 <= 640 ? (ovf ? PTRS_PICK(K, 8, true, 640) : PTRS_PICK(K, 8, false, 640)) : geom4 <= 1536 ? (ovf ? PTRS_PICK(K, 8, true, 1536) : PTRS_PICK(K, 8, false, 1536)) : (ovf ? PTRS_PICK(K, 8, true, 0) : PTRS_PICK(K, 8, false, 0))) \
-                                              : (ovf ? PTRS_PICK(K, 16, true, 0) : PTRS_PICK(K, 16, false, 0)))
+#define PTRS_PICK_OVF(K, D, GE) (form.ovf ? PTRS_PICK(K, D, true, GE) : PTRS_PICK(K, D, false, GE))
+#define PTRS_PICK_ALL(K) (form.depth == 9 ? PTRS_PICK(K, 9, false, LDS9_V4) : form.depth == 8 ? (form.geom == 640 ? PTRS_PICK_OVF(K, 8, 640) : form.geom == 1536 ? PTRS_PICK_OVF(K, 8, 1536) : PTRS_PICK_OVF(K, 8, 0)) : PTRS_PICK_OVF(K, 16, 0))
     // (fused_epilogue / fused_resolve = 0: the segment's epilogue / MIS resolve run as kernels of their own)
     typedef void (*EpilogueFn)(DParams, DScene, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *);
     struct ConnectFns { TravFn connect; void (*resolve)(DScene, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t *); };
-    template <int FEAT> TravFn pick_extend_t(bool v, bool ovf) { return PTRS_PICK_ALL(k_extend_rf); }
-    template <int FEAT> ConnectFns pick_connect_t(bool v, bool ovf) { return ConnectFns{PTRS_PICK_ALL(k_connect_rf), k_resolve<FEAT>}; }
+    template <int FEAT> TravFn pick_extend_t() { const bool v = form.vote; return PTRS_PICK_ALL(k_extend_rf); }
+    template <int FEAT> ConnectFns pick_connect_t() { const bool v = form.vote_connect; return ConnectFns{PTRS_PICK_ALL(k_connect_rf), k_resolve<FEAT>}; }
 #undef PTRS_PICK_ALL
+#undef PTRS_PICK_OVF
 #undef PTRS_PICK
-    // The one place where feat_trace becomes a template argument.  WHERE these functions stand is measured: the code object lists the template
-    // kernels in the order non-template code first names them, and epilogue_fn, pick_connect (with its resolve kernel) and pick_extend (defined
-    // behind ptrs_trace_rays) keep the earlier order.  Side by side here, the same kernels lie elsewhere: classroom's shade ran 0.8 % slower.
+    // The one place where feat_trace becomes a template argument.  (Where the kernels lie in the code object: k_code_object_order.)
     EpilogueFn epilogue_fn() const {
         static const EpilogueFn by_feat[3] = {k_epilogue<FEAT_FULL>, k_epilogue<FEAT_IMG_ENV>, k_epilogue<FEAT_SIMPLE>};
         return by_feat[feat_trace == FEAT_FULL ? 0 : feat_trace == FEAT_IMG_ENV ? 1 : 2];
     }
-    ConnectFns pick_connect(int ft, bool v, bool ovf) { return ft == FEAT_FULL ? pick_connect_t<FEAT_FULL>(v, ovf) : ft == FEAT_IMG_ENV ? pick_connect_t<FEAT_IMG_ENV>(v, ovf) : pick_connect_t<FEAT_SIMPLE>(v, ovf); }
-    TravFn pick_extend(int ft, bool v, bool ovf);
+    ConnectFns pick_connect() { return feat_trace == FEAT_FULL ? pick_connect_t<FEAT_FULL>() : feat_trace == FEAT_IMG_ENV ? pick_connect_t<FEAT_IMG_ENV>() : pick_connect_t<FEAT_SIMPLE>(); }
+    TravFn pick_extend() { return feat_trace == FEAT_FULL ? pick_extend_t<FEAT_FULL>() : feat_trace == FEAT_IMG_ENV ? pick_extend_t<FEAT_IMG_ENV>() : pick_extend_t<FEAT_SIMPLE>(); }
     StackSpill lane_spill() { StackSpill sp = ps->spill; if (sp.p) sp.p += (size_t)cur * ps->spill_lane_elems; return sp; } // this lane's columns
 
     void extend(uint32_t it) {
         t0(T_EXTEND);
         const StackSpill sp = lane_spill();
         const uint32_t epi_mask = opt.fused_epilogue ? kinds_mask : 0u; // non-zero: the kernel runs its segment's epilogue behind its last ray
-        const TravFn fn = pick_extend(feat_trace, vote, sp.p != nullptr);
+        const TravFn fn = pick_extend();
         hipLaunchKernelGGL(fn, dim3(persistent_grid(fn, T_EXTEND)), dim3(BLOCK), 0, stream, R, sc, sp, P, Q, it, seg_cap, refill, epi_mask, G, ticket(it, TK_EXTEND));
         if (!epi_mask) {
             t1(); t0(T_AUX); // the traversal span ends here: the epilogue is shading-side work
@@ -1979,7 +1777,7 @@ struct HipBackend {
         t0(T_CONNECT);
         const StackSpill sp = lane_spill();
         const uint32_t fused = (opt.fused_epilogue && opt.fused_resolve) ? 1u : 0u;
-        const ConnectFns cf = pick_connect(feat_trace, vote_connect, sp.p != nullptr);
+        const ConnectFns cf = pick_connect();
         const TravFn fn = cf.connect;
         hipLaunchKernelGGL(fn, dim3(persistent_grid(fn, T_CONNECT)), dim3(BLOCK), 0, stream, R, sc, sp, P, Q, it, seg_cap, refill_connect, fused, G, ticket(it, TK_CONNECT));
         if (!fused) {
@@ -2038,25 +1836,26 @@ struct HipBackend {
         const uint32_t nee_kinds = kinds_mask & 0x3fu & ~((1u << PTRS_MAT_MIRROR) | (1u << PTRS_MAT_GLASS));
         if (li == 0xffffffffu || !nee_kinds) return;
         t0(T_AUX);
-        if (feat == FEAT_IMG_ENV) hipLaunchKernelGGL((k_env_presample<FEAT_IMG_ENV>), dim3(persistent_grid(k_env_presample<FEAT_IMG_ENV>, T_AUX)), dim3(BLOCK), 0, stream, S, sc, P, Q, it, seg_cap, nee_kinds, li, shade_cfg(it), G, ticket(it, TK_PRESAMPLE));
-        else hipLaunchKernelGGL((k_env_presample<FEAT_FULL>), dim3(persistent_grid(k_env_presample<FEAT_FULL>, T_AUX)), dim3(BLOCK), 0, stream, S, sc, P, Q, it, seg_cap, nee_kinds, li, shade_cfg(it), G, ticket(it, TK_PRESAMPLE));
+        void (*const fn)(DSampler, DScene, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, ShadeLdsCfg, uint32_t, uint32_t *) = feat == FEAT_IMG_ENV ? k_env_presample<FEAT_IMG_ENV> : k_env_presample<FEAT_FULL>;
+        hipLaunchKernelGGL(fn, dim3(persistent_grid(fn, T_AUX)), dim3(BLOCK), 0, stream, S, sc, P, Q, it, seg_cap, nee_kinds, li, shade_cfg(it), G, ticket(it, TK_PRESAMPLE));
         t1();
     }
     // ---- the fused tail (k_tail) ----
     typedef void (*TailFn)(DParams, DSampler, DCamera, DScene, StackSpill, DPaths, DQueues, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, ShadeLdsCfg, uint32_t, uint32_t *);
     enum : uint32_t { TAIL_PATHS_DEFAULT = 192 }; // measured (tools/tail_sweep.sh): flat between 64 and 384 paths per segment for every job size; below, thin rounds stay three launches each, above, thick rounds run at the tail's two waves per SIMD
-    TailFn tail_fn() { // the instantiation for this scene, or null: one material bucket, the lean traversal kernels, the 8-entry stack column, the fused epilogue / resolve
-        if (!opt.tail || !opt.fused_epilogue || !opt.fused_resolve || !opt.shade_lds || !opt.persist || (ps->stack_lds != 8 && ps->stack_lds != 9) || feat_trace != FEAT_SIMPLE || S.kind != PTRS_SAMPLER_SOBOL) return nullptr;
+    // The instantiation for this scene's form, or null: one material bucket, the lean traversal kernels, the 8- or 9-entry stack column, the
+    // fused epilogue / resolve -- and the votes k_tail is compiled with (the extension stage votes, the connection stage by tail_votes_connect):
+    // under an explicit `vote` that asks for others the late rounds stay three launches each, which do what it says.
+    TailFn tail_fn() {
+        if (!opt.tail || !opt.fused_epilogue || !opt.fused_resolve || !opt.shade_lds || !opt.persist || form.depth == 16 || feat_trace != FEAT_SIMPLE || S.kind != PTRS_SAMPLER_SOBOL) return nullptr;
+        if (!form.vote || form.vote_connect != tail_votes_connect(form.geom)) return nullptr;
         int kind = -1;
         for (int k = 0; k < 7; ++k) if (ps->H.kinds_present[k]) { if (kind >= 0) return nullptr; kind = k; }
-        const bool ovf = ps->spill.p != nullptr;
-        if (ps->stack_lds == 9) return (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE) ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, LDS9_V4, false, 9> : nullptr;
-        if (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE) {
-            if (geom4 <= 640) return ovf ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 640, true> : (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 640, false>;
-            if (geom4 <= 1536) return ovf ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 1536, true> : (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 1536, false>;
-            return ovf ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 0, true> : (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, 0, false>;
-        }
-        if (kind == PTRS_MAT_DISNEY && feat == FEAT_IMG && geom4 > 1536) return ovf ? (TailFn)k_tail<PTRS_MAT_DISNEY, FEAT_IMG, 0, true> : (TailFn)k_tail<PTRS_MAT_DISNEY, FEAT_IMG, 0, false>;
+#define PTRS_TAIL(M, F, GE) (form.ovf ? (TailFn)k_tail<M, F, GE, true> : (TailFn)k_tail<M, F, GE, false>)
+        if (kind == PTRS_MAT_MATTE && feat == FEAT_SIMPLE)
+            return form.depth == 9 ? (TailFn)k_tail<PTRS_MAT_MATTE, FEAT_SIMPLE, LDS9_V4, false, 9> : form.geom == 640 ? PTRS_TAIL(PTRS_MAT_MATTE, FEAT_SIMPLE, 640) : form.geom == 1536 ? PTRS_TAIL(PTRS_MAT_MATTE, FEAT_SIMPLE, 1536) : PTRS_TAIL(PTRS_MAT_MATTE, FEAT_SIMPLE, 0);
+        if (kind == PTRS_MAT_DISNEY && feat == FEAT_IMG && form.geom == 0) return PTRS_TAIL(PTRS_MAT_DISNEY, FEAT_IMG, 0);
+#undef PTRS_TAIL
         return nullptr;
     }
     // The round at which the current pass (pass_begin has run: G is known) hands over to the tail, or 0xffffffff: the first round whose
@@ -2147,8 +1946,8 @@ struct HipBackend {
     void aov(uint32_t planes, uint32_t off) {
         t0(T_AUX);
         const DAov A = aov_arrays(aov_depth_plane(planes));
-        if (feat == FEAT_SIMPLE) hipLaunchKernelGGL((k_aov<FEAT_SIMPLE>), dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, C, sc, P, Q, A, off, seg_cap, G);
-        else hipLaunchKernelGGL((k_aov<FEAT_FULL>), dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, C, sc, P, Q, A, off, seg_cap, G);
+        void (*const fn)(DParams, DCamera, DScene, DPaths, DQueues, DAov, uint32_t, uint32_t, uint32_t) = feat == FEAT_SIMPLE ? k_aov<FEAT_SIMPLE> : k_aov<FEAT_FULL>;
+        hipLaunchKernelGGL(fn, dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, C, sc, P, Q, A, off, seg_cap, G);
         t1();
     }
     void film_aov(uint32_t planes, const DAovFilm &films, int32_t y0, int32_t y1, const DParams &Rf /* the sample rows and indices gathered: the pass, or in band mode one sample index of the band */) {
@@ -2191,7 +1990,7 @@ struct HipBackend {
         }
         st.ms_trace = st.ms_extend + st.ms_connect; st.ms_shade = st.ms_shade_kernels + st.ms_aux;
         st.queue_segments = G; st.lanes = n_lanes; st.grid_pct = (uint64_t)(opt.grid_pct ? opt.grid_pct : 100);
-        st.stack_lds = ps->stack_lds; st.lds_form_v4 = geom4 == 0xffffffffu ? 0u : geom4;
+        st.stack_lds = (uint64_t)form.depth; st.lds_form_v4 = form.v4;
         { const int cls[4] = {T_EXTEND, T_CONNECT, T_SHADE, T_AUX}; for (int k = 0; k < 4; ++k) { st.grid_wgs[k] = last_grid[cls[k]]; st.resident_wgs_per_cu[k] = last_per_cu[cls[k]]; } }
         st.extend_launches = cat_launches[T_EXTEND]; st.connect_launches = cat_launches[T_CONNECT]; st.shade_launches = cat_launches[T_SHADE]; st.aux_launches = cat_launches[T_AUX]; st.film_launches = cat_launches[T_FILM]; st.tail_launches = cat_launches[T_TAIL]; st.tail_round = tail_at_last;
         size_t bytes = 0;
@@ -2934,8 +2733,6 @@ int ptrs_render_dump_rays(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
     });
 }
 
-HipBackend::TravFn HipBackend::pick_extend(int ft, bool v, bool ovf) { return ft == FEAT_FULL ? pick_extend_t<FEAT_FULL>(v, ovf) : ft == FEAT_IMG_ENV ? pick_extend_t<FEAT_IMG_ENV>(v, ovf) : pick_extend_t<FEAT_SIMPLE>(v, ovf); } // (here: see epilogue_fn)
-
 // Traversal alone, the way a frame runs it: the rays are uploaded once, laid out as one pass's path state with an extension queue in
 // segments (64-ray blocks dealt round-robin, like k_generate's), and the lane-refill extension kernel of this scene (phase voting,
 // LDS-cached top / LDS form, persistent waves with tickets; no epilogue) is launched `repeats` times with an event pair each.
@@ -2981,7 +2778,7 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         DQueues Q; std::memset(&Q, 0, sizeof(Q)); Q.ext[0] = (uint32_t *)bq.p; Q.counts = (uint32_t *)bc.p; Q.stats = (unsigned long long *)bs.p; Q.tickets = (uint32_t *)bt.p; Q.alive = (uint32_t *)bt.p + (size_t)(repeats + 1) * TK_LAUNCH_WORDS;
         DParams R; std::memset(&R, 0, sizeof(R)); R.n_paths = n;
         StackSpill sp = scene->spill;
-        const HipBackend::TravFn fn = be.pick_extend(be.feat_trace, be.vote, sp.p != nullptr);
+        const HipBackend::TravFn fn = be.pick_extend();
         const uint32_t grid = be.persistent_grid(fn, HipBackend::T_EXTEND);
         std::vector<hipEvent_t> ev(2 * (size_t)repeats, nullptr);
         for (auto &x : ev) if (e == hipSuccess) e = hipEventCreate(&x); // (destroyed below on every path: nothing between here and there returns)
@@ -3013,7 +2810,7 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         }
         stats->ms_trace = ms; stats->ms_extend = ms; stats->trace_launches = repeats; stats->extend_launches = repeats; stats->kernel_launches = repeats + 1; stats->rays_extension = (uint64_t)n * repeats;
         stats->queue_segments = G; stats->grid_wgs[0] = grid; stats->resident_wgs_per_cu[0] = be.last_per_cu[HipBackend::T_EXTEND];
-        stats->stack_lds = scene->stack_lds; stats->lds_form_v4 = be.geom4 == 0xffffffffu ? 0u : be.geom4;
+        stats->stack_lds = (uint64_t)be.form.depth; stats->lds_form_v4 = be.form.v4;
         return PTRS_OK;
     });
 }

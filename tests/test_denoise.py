@@ -36,7 +36,7 @@ DEFAULTS = dict(iterations=5, sigma_color=0.25, sigma_normal=0.3, sigma_depth=0.
 # dropped in turn): worst 8.35e-7, on the Cornell input (a float32 numpy prototype of the formulas measured 7.7e-7).  The bound is 8 x that, rounded up to a
 # power of two.
 TWIN_VS_F64 = 2.0 ** -17
-# the LDS form's tile: 64 columns x 8 lattice rows of outputs (ptrs_hip.hip: DN_TILE_W, DN_TILE_T), for steps up to 16
+# the LDS form's tile: 64 columns x 8 lattice rows of outputs (pt_hip_post.h: DN_TILE_W, DN_TILE_T), for steps up to 16
 TILE_W, TILE_T, LDS_STEPS = 64, 8, (1, 2, 4, 8, 16)
 
 

@@ -109,20 +109,24 @@ def test_band_and_pass_decomposition_is_exact(ptrs, orc):
     assert np.array_equal(cam.film.pixels["weight"].view(np.uint32), film_full["weight"].view(np.uint32))
 
 
-def _gpu_vs_oracle(ptrs, orc, cam, scene, spp, depth, **opts):
+def _gpu_vs_oracle(ptrs, orc, cam, scene, spp, depth, expect_tail=True, oracle=None, **opts):
+    """Returns the oracle's render, which a caller with several cases of one scene and size hands back in as `oracle`."""
     integ = ptrs.PathIntegrator(ptrs.SamplerBuilder(spp, cam.film.get_sample_bounds()), depth)
     with ptrs.options(**opts):
         samples = integ.render(cam, scene, want_samples=True)
     st = integ.last_stats
     if "lanes" in opts:
         assert st.lanes == opts["lanes"]
-    if "tail_at" in opts:
+    if "tail_at" in opts and expect_tail:
         assert st.tail_launches == st.passes and st.tail_round == opts["tail_at"], "the scene has no fused-tail instantiation"
-    film_ref, ref, ost = orc.OracleScene(scene).render(cam, orc.make_params(cam.film.width, cam.film.height, spp, depth), n_threads=8, want_samples=True)
+    elif "tail_at" in opts:
+        assert st.tail_launches == 0, "k_tail ran with a vote policy it is not compiled with"
+    film_ref, ref, ost = oracle or orc.OracleScene(scene).render(cam, orc.make_params(cam.film.width, cam.film.height, spp, depth), n_threads=8, want_samples=True)
     assert (st.samples, st.rays_extension, st.rays_shadow, st.rays_mis) == (ost.samples, ost.rays_extension, ost.rays_shadow, ost.rays_mis)
     bad = (samples.view(np.uint32) != ref.view(np.uint32)).any(axis=-1)
     assert bad.sum() == 0, "%d of %d samples differ" % (bad.sum(), bad.size)
     assert rel_l2(cam.film.to_rgb(), film_ref["rgb"] / film_ref["weight"][..., None]) < 1e-5
+    return film_ref, ref, ost
 
 
 def test_material_zoo_matches_oracle(ptrs, orc, scenes):
@@ -154,14 +158,20 @@ def test_fused_tail_matches_oracle(ptrs, orc, scenes):
     rounds in one launch.  Held against the oracle sample by sample for every form it is instantiated for: the LDS form (Cornell),
     quad nodes out of global memory for a Matte scene (Cornell with node_form = 2) and for Disney + image textures (colonnade);
     from round 0 (the whole pass in one launch), from a middle round, on one lane and on four; and placed by the scene's
-    learned survival profile (second render of a scene)."""
-    def run(cam, scene, spp, depth, **opts):
-        _gpu_vs_oracle(ptrs, orc, cam, scene, spp, depth, **opts)
-    for opts in ({"tail_at": 0}, {"tail_at": 2, "lanes": 4}, {"tail_at": 7}, {"tail_at": 1, "node_form": 2}):
+    learned survival profile (second render of a scene).  k_tail is compiled with ONE vote policy -- the extension stage votes, the
+    connection stage votes for quad nodes only -- so an explicit `vote` that asks for another leaves the late rounds to the three
+    launches per round, which do what it says: no tail launch then, and the same samples."""
+    def run(cam, scene, spp, depth, expect_tail=True, oracle=None, **opts):
+        return _gpu_vs_oracle(ptrs, orc, cam, scene, spp, depth, expect_tail=expect_tail, oracle=oracle, **opts)
+    oracle = None  # (one Cornell render of the oracle serves all cases of this size)
+    for opts, expect_tail in (({"tail_at": 0}, True), ({"tail_at": 2, "lanes": 4}, True), ({"tail_at": 7}, True), ({"tail_at": 1, "node_form": 2}, True),
+                              ({"vote": 0, "tail_at": 0}, False), ({"vote": 1, "tail_at": 0}, False), ({"vote": 2, "tail_at": 0}, True),  # (LDS form: the tail's connection stage does not vote)
+                              ({"node_form": 2, "vote": 1, "tail_at": 1}, True), ({"node_form": 2, "vote": 2, "tail_at": 1}, False)):
         cam, scene = ptrs.import_scene(CORNELL, (64, 64))  # (a fresh scene: node_form is read when the device scene is created, inside the render)
-        run(cam, scene, 8, 15, **opts)
+        oracle = run(cam, scene, 8, 15, expect_tail=expect_tail, oracle=oracle, **opts)
     # the learned placement: the first render of a scene runs round by round and leaves the profile, the second hands over where the
-    # profile says a segment holds at most tail_paths paths -- here, with 16 384 segments for 37 k paths, at round 0
+    # profile says a segment holds at most tail_paths paths -- here, where 37 k paths make fewer 64-path chunks than a pass has
+    # segments and every segment holds one chunk, at round 0
     cam, scene = ptrs.import_scene(CORNELL, (64, 64))
     integ = ptrs.PathIntegrator(ptrs.SamplerBuilder(8, cam.film.get_sample_bounds()), 15)
     integ.render(cam, scene)
@@ -170,8 +180,7 @@ def test_fused_tail_matches_oracle(ptrs, orc, scenes):
     s2 = integ.render(cam, scene, want_samples=True)
     st = integ.last_stats
     assert st.tail_launches == st.passes and st.tail_round == 0
-    _, ref, _ = orc.OracleScene(scene).render(cam, orc.make_params(64, 64, 8, 15), n_threads=8, want_samples=True)
-    assert np.array_equal(s2.view(np.uint32), ref.view(np.uint32))
+    assert np.array_equal(s2.view(np.uint32), oracle[1].view(np.uint32))
     cam, scene = scenes.colonnade((160, 90))
     run(cam, scene, 4, 15, tail_at=0)
     run(cam, scene, 4, 15, tail_at=3, lanes=4)
