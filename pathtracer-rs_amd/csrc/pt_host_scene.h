@@ -352,23 +352,29 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
             // finite origin and any direction, infinite reciprocals included), so traversal needs no test for REF_NONE
             static DNode4 blank() { DNode4 d; std::memset(&d, 0, sizeof(d)); for (int s = 0; s < 4; ++s) { d.ref[s] = REF_NONE; for (int k = 0; k < 3; ++k) { d.box[(2 * k) * 4 + s] = PT_INF; d.box[(2 * k + 1) * 4 + s] = -PT_INF; } } return d; }
             // reference to a leaf range; ranges longer than REF_MAX_LEAF (only possible when many centroids coincide)
-            // become quad nodes whose slots are consecutive chunks sharing the leaf's box, visited in order and
-            // popped without the entry re-test (the reference tests such a leaf's box once)
-            uint32_t leaf_ref(const DNode &leaf, uint32_t first, uint32_t count) {
+            // become quad nodes whose slots are consecutive chunks, visited in order.  The reference tests such a leaf's box once,
+            // against the t_max of that moment, and then all its triangles: that one test is the slot of the leaf in its parent, so
+            // the chunk nodes -- nested ones included -- carry the box nothing can miss, (-inf, +inf), for their slots.  Its slab
+            // test gives the entry distance -inf, which passes `t_entry < t_max` at the visit and at the pop, however far a hit
+            // inside the leaf has brought t_max down (a repeated leaf box fails it once a hit lies on the box's face, and the rest
+            // of the leaf would go untested: ties between coincident triangles then go to the wrong one)
+            static DNode everything() { DNode e; std::memset(&e, 0, sizeof(e)); e.pmin[0] = e.pmin[1] = e.pmin[2] = -PT_INF; e.pmax0 = e.pmax1 = e.pmax2 = PT_INF; return e; }
+            uint32_t leaf_ref(uint32_t first, uint32_t count) {
                 if (count <= REF_MAX_LEAF) return REF_LEAF | ((count - 1u) << REF_COUNT_SHIFT) | first;
                 const uint32_t me = (uint32_t)out.size();
                 out.push_back(blank());
                 DNode4 d = blank(); d.axes = 3u | (3u << 2) | (3u << 4) | 0x100u;
                 const uint32_t per = (count + 3u) / 4u;
+                const DNode all = everything();
                 uint32_t at = first, left = count;
-                for (int s = 0; s < 4 && left; ++s) { const uint32_t c = std::min(per, left); set_slot(d, s, leaf, leaf_ref(leaf, at, c)); at += c; left -= c; }
+                for (int s = 0; s < 4 && left; ++s) { const uint32_t c = std::min(per, left); set_slot(d, s, all, leaf_ref(at, c)); at += c; left -= c; }
                 out[me] = d;
                 return me;
             }
             uint32_t ref_of(uint32_t i) { // reference for binary-tree node i
                 const DNode &nd = n[i];
                 const uint32_t np = nd.meta & 0xffffu;
-                if (np) return leaf_ref(nd, nd.offset, np);
+                if (np) return leaf_ref(nd.offset, np);
                 const uint32_t me = (uint32_t)out.size();
                 out.push_back(blank());
                 DNode4 d = blank();
@@ -376,7 +382,7 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
                 uint32_t ax[2] = {3u, 3u};
                 for (int g = 0; g < 2; ++g) {
                     const DNode &c = n[kid[g]];
-                    if (c.meta & 0xffffu) set_slot(d, 2 * g, c, leaf_ref(c, c.offset, c.meta & 0xffffu));
+                    if (c.meta & 0xffffu) set_slot(d, 2 * g, c, leaf_ref(c.offset, c.meta & 0xffffu));
                     else { ax[g] = (c.meta >> 16) & 0xffu; set_slot(d, 2 * g, n[kid[g] + 1], ref_of(kid[g] + 1)); set_slot(d, 2 * g + 1, n[c.offset], ref_of(c.offset)); }
                 }
                 d.axes = ((nd.meta >> 16) & 3u) | (ax[0] << 2) | (ax[1] << 4);
@@ -385,11 +391,11 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
             }
         } conv{H.nodes, H.nodes4};
         H.nodes4.reserve(H.nodes.size() / 3 + 2);
-        const uint32_t root = conv.ref_of(0);
-        if (root & REF_LEAF) { // the whole scene is one leaf: a node whose only slot is that leaf
-            DNode4 d = Conv::blank(); Conv::set_slot(d, 0, H.nodes[0], root); d.axes = 3u | (3u << 2) | (3u << 4);
-            H.nodes4.insert(H.nodes4.begin(), d);
-        }
+        if (H.nodes[0].meta & 0xffffu) { // the whole scene is one leaf: a node whose only slot is that leaf, with the leaf's box (an over-long leaf's chunk nodes do not carry it)
+            H.nodes4.push_back(Conv::blank());
+            DNode4 d = Conv::blank(); Conv::set_slot(d, 0, H.nodes[0], conv.leaf_ref(H.nodes[0].offset, H.nodes[0].meta & 0xffffu)); d.axes = 3u | (3u << 2) | (3u << 4);
+            H.nodes4[0] = d;
+        } else conv.ref_of(0);
         if (H.nodes4.size() >= (1u << 25)) return bad("too many quad nodes for 32-bit node offsets (2^25 x 128 bytes)"); // GeomGlobal::quad_load
         for (DNode4 &d : H.nodes4) { uint32_t c = 0; for (int sl = 0; sl < 4; ++sl) c += d.ref[sl] != REF_NONE ? 1u : 0u; d.axes = (d.axes & 0xfffu) | (c << 12); } // bits 12-14: occupied slots (the boxes-tested statistic)
         // pad[0]: the three split axes once more as one-hot bytes (bit a of byte k set when split k runs along axis a, 0 = never swap): with the
@@ -417,24 +423,26 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
                 else { d.c1min0 = mn[0]; d.c1min1 = mn[1]; d.c1min2 = mn[2]; d.c1max[0] = mx[0]; d.c1max[1] = mx[1]; d.c1max[2] = mx[2]; d.ref1 = ref; }
             }
             // reference to a leaf range; ranges longer than REF_MAX_LEAF (only possible when many centroids
-            // coincide) become a balanced subtree of pair nodes that share the leaf's box and keep the triangle order
-            uint32_t leaf_ref(uint32_t first, uint32_t count, const float mn[3], const float mx[3]) {
+            // coincide) become a balanced subtree of pair nodes that keeps the triangle order.  The leaf's own box is tested once,
+            // where its parent holds it; the subtree's nodes carry the box nothing can miss, (-inf, +inf), for both children (entry
+            // distance -inf: passes `t_entry < t_max` at the visit and at the pop, see the quad form's leaf_ref)
+            uint32_t leaf_ref(uint32_t first, uint32_t count) {
                 if (count <= REF_MAX_LEAF) return REF_LEAF | ((count - 1u) << REF_COUNT_SHIFT) | first;
                 uint32_t me = (uint32_t)out.size();
                 out.push_back(DNode2());
                 DNode2 d; std::memset(&d, 0, sizeof(d));
                 const uint32_t half = count / 2u; // balanced, order-preserving split
-                uint32_t r0 = leaf_ref(first, half, mn, mx);
-                uint32_t r1 = leaf_ref(first + half, count - half, mn, mx);
+                uint32_t r0 = leaf_ref(first, half);
+                uint32_t r1 = leaf_ref(first + half, count - half);
+                const float mn[3] = {-PT_INF, -PT_INF, -PT_INF}, mx[3] = {PT_INF, PT_INF, PT_INF};
                 set_child(d, 0, mn, mx, r0); set_child(d, 1, mn, mx, r1); d.axis = 3; // axis 3: never "negative" -> first child first
                 out[me] = d;
                 return me;
             }
             uint32_t ref_of(uint32_t i) { // reference for binary-tree node i
                 const DNode &nd = n[i];
-                float mn[3], mx[3]; box_of(nd, mn, mx);
                 const uint32_t np = nd.meta & 0xffffu;
-                if (np) return leaf_ref(nd.offset, np, mn, mx);
+                if (np) return leaf_ref(nd.offset, np);
                 uint32_t me = (uint32_t)out.size();
                 out.push_back(DNode2());
                 DNode2 d; std::memset(&d, 0, sizeof(d));
@@ -448,13 +456,13 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
         } conv{H.nodes, H.nodes2};
         if (n_tris > REF_FIRST_MASK) return bad("too many triangles for the leaf reference encoding");
         H.nodes2.reserve(H.nodes.size() / 2 + 2);
-        const uint32_t root = conv.ref_of(0);
-        if (root & REF_LEAF) { // the whole scene is one leaf: give it a parent whose second child is absent
+        if (H.nodes[0].meta & 0xffffu) { // the whole scene is one leaf: give it a parent that holds its box and whose second child is absent
+            H.nodes2.push_back(DNode2());
             DNode2 d; std::memset(&d, 0, sizeof(d));
             float mn[3], mx[3]; Conv::box_of(H.nodes[0], mn, mx);
-            Conv::set_child(d, 0, mn, mx, root); d.ref1 = REF_NONE; d.axis = 3;
-            H.nodes2.insert(H.nodes2.begin(), d);
-        }
+            Conv::set_child(d, 0, mn, mx, conv.leaf_ref(H.nodes[0].offset, H.nodes[0].meta & 0xffffu)); d.ref1 = REF_NONE; d.axis = 3;
+            H.nodes2[0] = d;
+        } else conv.ref_of(0);
         // stack bound = depth of the pair-node tree
         std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0u, 1u});
         uint32_t depth2 = 0;

@@ -36,8 +36,10 @@ static_assert(sizeof(DNode2) == 64, "node2");
 // occupies slot 0 (or 2) and slot 1 (or 3) is REF_NONE.  The boxes are stored PER AXIS: box[(2 a + u) * 4 + s] = lower (u = 0) / upper
 // (u = 1) plane of slot s on axis a -- six vectors of four slots each, so that a ray reads, per axis, the vector of the planes it meets
 // first and the vector of those it meets last (by the sign of its direction) instead of selecting 24 planes after the fetch.
-// axes: bits 0-1 split axis of the node, 2-3 of A, 4-5 of B (3 = never swap); bit 8: entries stacked from this node
-// are popped without the entry-distance re-test (chunks of one over-long leaf share the leaf's box); bits 12-14: number of
+// axes: bits 0-1 split axis of the node, 2-3 of A, 4-5 of B (3 = never swap); bit 8: a chunk node of one over-long leaf: its slots
+// are stacked with the entry distance -FLT_MAX.  That alone never kept such a leaf whole -- the node visit's own `t_entry < t_max` and
+// a nested chunk node's visit still failed a repeated leaf box -- so the host gives these slots the box (-inf, +inf), whose entry
+// distance is -inf at the visit and at the pop (pt_host_scene.h leaf_ref); the bit now changes no result; bits 12-14: number of
 // occupied slots.  An empty slot (ref REF_NONE) holds the box (+inf, -inf), which no ray enters.
 // Visiting [near group: near slot, far slot][far group: near slot, far slot] reproduces the binary traversal's
 // order (accelerator.rs:397-408) with half the dependent fetches.

@@ -37,6 +37,17 @@ struct CheckedStack {
     void clear() { n = 0; }
 };
 
+// traversal stack of twin_trace_rays: records the peak occupancy and refuses -- with an error, instead of writing -- a push past the
+// host's stack_bound (what the GPU sizes its LDS column and its spill columns from) or past its own capacity
+struct CountingStack {
+    uint32_t s[128]; float te[128]; int n = 0; int cap = 128; uint32_t *peak = nullptr; bool *overflow = nullptr;
+    void push(uint32_t v, float t) { if (n >= cap) { *overflow = true; return; } s[n] = v; te[n] = t; ++n; if ((uint32_t)n > *peak) *peak = (uint32_t)n; }
+    void pop(uint32_t &v, float &t) { --n; v = s[n]; t = te[n]; }
+    bool empty() const { return n == 0; }
+    void clear() { n = 0; }
+};
+uint32_t g_peak_stack = 0; // most entries any ray of the last twin_trace_rays call had stacked
+
 struct HostBackend {
     bool overflow = false, err_dim = false; int stack_cap = 128;
     CheckedStack make_stack() { CheckedStack k; k.cap = stack_cap; k.overflow = &overflow; return k; }
@@ -165,16 +176,19 @@ int twin_load_tables(const char *path) {
 void twin_use_bytetab(int on) { g_use_bytetab = on != 0; }
 void twin_force_full_features(int on) { g_force_full = on != 0; }
 
-int twin_scene_create(const PtrsSceneDesc *d, void **out) {
+// node_form as the library's option of that name: 0 = by size, 2 = quad nodes whatever the size
+int twin_scene_create_form(const PtrsSceneDesc *d, int32_t node_form, void **out) {
     auto *s = new TwinScene();
-    int rc = build_host_scene(*d, s->H, g_err);
+    int rc = build_host_scene(*d, s->H, g_err, node_form);
     if (rc != PTRS_OK) { delete s; return rc; }
     s->sc = host_scene_view(s->H);
     *out = s;
     return PTRS_OK;
 }
+int twin_scene_create(const PtrsSceneDesc *d, void **out) { return twin_scene_create_form(d, 0, out); }
 void twin_scene_destroy(void *s) { delete static_cast<TwinScene *>(s); }
-void twin_scene_info(void *s, uint32_t *max_depth, uint32_t *stack_bound, uint32_t *n_nodes2) { auto *t = static_cast<TwinScene *>(s); *max_depth = t->H.max_depth; *stack_bound = t->H.stack_bound; *n_nodes2 = (uint32_t)(t->H.nodes2.size() + t->H.nodes4.size()); }
+// returns 1 when the scene is walked in quad form, 0 for pair form
+int twin_scene_info(void *s, uint32_t *max_depth, uint32_t *stack_bound, uint32_t *n_nodes2) { auto *t = static_cast<TwinScene *>(s); *max_depth = t->H.max_depth; *stack_bound = t->H.stack_bound; *n_nodes2 = (uint32_t)(t->H.nodes2.size() + t->H.nodes4.size()); return t->H.use_quad ? 1 : 0; }
 
 int twin_render(void *sp, const PtrsCamera *cam, const PtrsRenderParams *prm, PtrsFilmPixel *film, float *sample_rgb, PtrsStats *stats) {
     if (!g_tables.ok) { g_err = "tables not loaded"; return PTRS_ERR_INVALID; }
@@ -191,16 +205,21 @@ int twin_render(void *sp, const PtrsCamera *cam, const PtrsRenderParams *prm, Pt
 int twin_trace_rays(void *sp, uint32_t n, const float *rays, int32_t any_hit, PtrsHit *hits, PtrsStats *stats) {
     TwinScene *s = static_cast<TwinScene *>(sp);
     uint64_t nodes = 0, tris = 0;
+    bool overflow = false;
+    g_peak_stack = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        LocalStack stk; HitRec h; uint32_t nn = 0, nt = 0;
+        CountingStack stk; stk.cap = (int)std::min<uint32_t>(s->H.stack_bound, 128u); stk.peak = &g_peak_stack; stk.overflow = &overflow; // exactly the host's bound, as in twin_render
+        HitRec h; uint32_t nn = 0, nt = 0;
         f3 o = mk3(rays[7 * i], rays[7 * i + 1], rays[7 * i + 2]), d = mk3(rays[7 * i + 3], rays[7 * i + 4], rays[7 * i + 5]);
         bool hit = any_hit ? bvh_trace<true>(s->sc, o, d, rays[7 * i + 6], stk, h, nn, nt) : bvh_trace<false>(s->sc, o, d, rays[7 * i + 6], stk, h, nn, nt);
         nodes += nn; tris += nt;
         hits[i].prim = any_hit ? (hit ? 0 : -1) : h.prim; hits[i].t = h.t; hits[i].b0 = h.b0; hits[i].b1 = h.b1; hits[i].b2 = h.b2;
     }
     if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->nodes_visited = nodes; stats->tris_tested = tris; }
+    if (overflow) { g_err = "traversal stack overflow: a push past stack_bound = " + std::to_string(s->H.stack_bound) + " (would corrupt LDS or the spill columns on the GPU)"; return PTRS_ERR_INVALID; }
     return PTRS_OK;
 }
+uint32_t twin_peak_stack(void) { return g_peak_stack; }
 
 int twin_sobol_samples(const PtrsRenderParams *prm, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sample_nums, const uint32_t *dims, float *out, uint64_t *index_out) {
     if (!g_tables.ok) { g_err = "tables not loaded"; return PTRS_ERR_INVALID; }

@@ -34,10 +34,11 @@ def round_up_pow2(v):
 
 
 class TwinScene:
-    def __init__(self, render_scene, bvh=None):
+    def __init__(self, render_scene, bvh=None, node_form=0):
+        """node_form: the library's option of that name (0 = by size, 2 = quad nodes whatever the size)."""
         self._h = C.c_void_p()
         desc = render_scene.desc(bvh)
-        _check(lib().twin_scene_create(C.byref(desc), C.byref(self._h)))
+        _check(lib().twin_scene_create_form(C.byref(desc), C.c_int32(int(node_form)), C.byref(self._h)))
 
     def __del__(self):
         try:
@@ -45,6 +46,13 @@ class TwinScene:
                 lib().twin_scene_destroy(self._h)
         except Exception:
             pass
+
+    def info(self):
+        """twin_scene_info: max_depth, stack_bound (what the device sizes its stack columns from), the node count of the traversal
+        form, and which form that is."""
+        d, b, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        q = lib().twin_scene_info(self._h, C.byref(d), C.byref(b), C.byref(n))
+        return dict(max_depth=d.value, stack_bound=b.value, n_nodes=n.value, quad=bool(q))
 
     def render(self, camera, params, want_samples=False, film=None):
         W, H = params.width, params.height
@@ -64,6 +72,14 @@ class TwinScene:
         stats = abi.PtrsStats()
         _check(lib().twin_trace_rays(self._h, rays.shape[0], C.c_void_p(rays.ctypes.data), int(any_hit), C.c_void_p(hits.ctypes.data), C.byref(stats)))
         return hits, stats
+
+
+def peak_stack():
+    """twin_peak_stack: the most entries any ray of the last trace_rays call had on its traversal stack (a push past the scene's
+    stack_bound makes that call fail instead)."""
+    L = lib()
+    L.twin_peak_stack.restype = C.c_uint32
+    return int(L.twin_peak_stack())
 
 
 def sobol_samples(params, px, py, sample_nums, dims):
