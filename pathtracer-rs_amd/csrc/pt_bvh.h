@@ -57,13 +57,29 @@ struct GeomLocal {
 // stays in the reference's running value to the end and fails the box (t_max > 0 is false for a NaN t_max; for a NaN t_min the entry
 // distance is NaN and the caller's t_entry < ray.t_max is false): the explicit `ordered` test fails the box in exactly those cases
 // (test_rays_inside_box_planes).  (+0 / -0 can come out differently in the entry distance; it is only ever compared.)
+PT_HD void slab_ends(float tx_min, float ty_min, float tz_min, float tx_max, float ty_max, float tz_max, float &tn, float &tf) { // the largest lower end, the smallest upper end
+    tn = __builtin_fmaxf(__builtin_fmaxf(tx_min, ty_min), tz_min);
+    tf = __builtin_fminf(__builtin_fminf(tx_max, ty_max), tz_max);
+}
 PT_HD bool slab_finish(float tx_min, float ty_min, float tz_min, float tx_max, float ty_max, float tz_max, float &t_entry) {
     const bool x_ordered = !__builtin_isunordered(tx_min, tx_max);
-    const float tn = __builtin_fmaxf(__builtin_fmaxf(tx_min, ty_min), tz_min);
-    const float tf = __builtin_fminf(__builtin_fminf(tx_max, ty_max), tz_max);
+    float tn, tf;
+    slab_ends(tx_min, ty_min, tz_min, tx_max, ty_max, tz_max, tn, tf);
     t_entry = tn;
     return (tn <= tf) & (tf > 0.0f) & x_ordered;
 }
+#if defined(__HIPCC__) || defined(__HIP__)
+// slab_finish with its decision as a lane mask of the wave, for callers that go on combining masks (ptrs_hip.hip: lf_node_visit).  A
+// boolean that is a conjunction of compares reaches a ballot as a 0 / 1 integer in a vector register (v_cndmask_b32 0, 1 + v_cmp_ne_u32:
+// two half-rate instructions that rebuild a mask the compiler already held in a scalar register pair); the ballot of ONE compare is that
+// compare's own register pair, and the conjunction of ballots is s_and_b64.  Same three compares on the same values: same decision.
+__device__ inline unsigned long long slab_finish_mask(float tx_min, float ty_min, float tz_min, float tx_max, float ty_max, float tz_max, float &t_entry) {
+    float tn, tf;
+    slab_ends(tx_min, ty_min, tz_min, tx_max, ty_max, tz_max, tn, tf);
+    t_entry = tn;
+    return __builtin_amdgcn_ballot_w64(tn <= tf) & __builtin_amdgcn_ballot_w64(tf > 0.0f) & __builtin_amdgcn_ballot_w64(!__builtin_isunordered(tx_min, tx_max));
+}
+#endif
 // Bounds3::intersect_p_precomp (bounds.rs:190-232) on explicit box corners, split in two: everything
 // that does not depend on ray.t_max (the per-axis interval tests and `t_max_box > 0`) is decided here
 // and the entry distance returned; the caller finishes the test with `t_entry < ray.t_max`.

@@ -321,20 +321,31 @@ __device__ inline LdsGeom stage_lds_form(const DScene &sc, v4 *lds) {
 
 // pair_visit on the LDS form: both children's slab tests from the ray's three plane records, the far child stacked with its entry
 // distance when both are hit (pop-time re-test, accelerator.rs:372), the visiting order from the split axis' sign bit.
-template <class Stack>
+// MASKS (see StepMasks below): the two decisions as lane masks from the start; else as booleans whose ballots are taken here.
+template <bool MASKS, class Stack>
 __device__ inline void lf_node_visit(uint32_t &cur, f3 o, f3 inv, uint32_t ox, uint32_t oy, uint32_t oz, uint32_t negbits, float t_max, Stack &stack, uint32_t &n_nodes) {
     const v4 X = lds_at(cur + ox), Y = lds_at(cur + oy), Z = lds_at(cur + oz), Rf = lds_at(cur + 96u);
     const float k = 1.0f + 2.0f * gamma_err(3);
     n_nodes += 2;
     float t0, t1;
-    bool h0 = slab_finish((X.x - o.x) * inv.x, (Y.x - o.y) * inv.y, (Z.x - o.z) * inv.z, ((X.y - o.x) * inv.x) * k, ((Y.y - o.y) * inv.y) * k, ((Z.y - o.z) * inv.z) * k, t0);
-    bool h1 = slab_finish((X.z - o.x) * inv.x, (Y.z - o.y) * inv.y, (Z.z - o.z) * inv.z, ((X.w - o.x) * inv.x) * k, ((Y.w - o.y) * inv.y) * k, ((Z.w - o.z) * inv.z) * k, t1);
-    h0 = h0 & (t0 < t_max); h1 = h1 & (t1 < t_max);
+    // The two decisions as lane masks from the start (slab_finish_mask: the ballots of the single compares, combined in scalar registers), and
+    // h0 & h1, h0 | h1 on the masks themselves -- s_and_b64 / s_or_b64 -- instead of the 0 / 1 integers in vector registers the compiler makes
+    // of a boolean that is a conjunction of compares when it reaches a ballot or feeds several branches.
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    bool h0, h1 = false;
+    if (MASKS) {
+        m0 = slab_finish_mask((X.x - o.x) * inv.x, (Y.x - o.y) * inv.y, (Z.x - o.z) * inv.z, ((X.y - o.x) * inv.x) * k, ((Y.y - o.y) * inv.y) * k, ((Z.y - o.z) * inv.z) * k, t0);
+        m1 = slab_finish_mask((X.z - o.x) * inv.x, (Y.z - o.y) * inv.y, (Z.z - o.z) * inv.z, ((X.w - o.x) * inv.x) * k, ((Y.w - o.y) * inv.y) * k, ((Z.w - o.z) * inv.z) * k, t1);
+        m0 &= __builtin_amdgcn_ballot_w64(t0 < t_max); m1 &= __builtin_amdgcn_ballot_w64(t1 < t_max);
+        h0 = __builtin_amdgcn_inverse_ballot_w64(m0);
+    } else {
+        h0 = slab_finish((X.x - o.x) * inv.x, (Y.x - o.y) * inv.y, (Z.x - o.z) * inv.z, ((X.y - o.x) * inv.x) * k, ((Y.y - o.y) * inv.y) * k, ((Z.y - o.z) * inv.z) * k, t0);
+        h1 = slab_finish((X.z - o.x) * inv.x, (Y.z - o.y) * inv.y, (Z.z - o.z) * inv.z, ((X.w - o.x) * inv.x) * k, ((Y.w - o.y) * inv.y) * k, ((Z.w - o.z) * inv.z) * k, t1);
+        h0 = h0 & (t0 < t_max); h1 = h1 & (t1 < t_max);
+    }
     const uint32_t ref0 = f2u(Rf.x), ref1 = f2u(Rf.y);
     const bool second_first = (negbits & f2u(Rf.z)) != 0u;
-    // (h0 & h1, h0 | h1 on the lane masks themselves -- s_and_b64 / s_or_b64 -- instead of the 0 / 1 integers in vector registers the
-    // compiler makes of two booleans that feed several branches)
-    const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
+    if (!MASKS) { m0 = __ballot(h0); m1 = __ballot(h1); } // (behind the loads above, where the boolean form has always taken them)
     if (Stack::select_push) { // no divergent region around the push and the one-child case: selects, one unconditional LDS store, and the pop as the only branch
         const bool both = __builtin_amdgcn_inverse_ballot_w64(m0 & m1);
         stack.push_if(both, second_first ? ref0 : ref1, second_first ? t0 : t1);
@@ -373,32 +384,61 @@ __device__ inline bool lf_leaf_step(const DScene &sc, uint32_t &leaf, f3 op, flo
     return ok & any_rt;
 }
 // The vote of rf_step / lf_step: which lanes of the wave wait for a node visit and which for a triangle test; true when the visit has the majority.
-__device__ inline bool vote_node_phase(uint32_t r_cur, bool &at_node, bool &at_leaf) {
-    at_node = (int32_t)r_cur >= 0; at_leaf = (int32_t)r_cur < -1; // leaf references have bit 31 set; lanes without a ray hold REF_NONE = -1
-    const uint32_t n_node = rfl((uint32_t)__popcll(__ballot(at_node))), n_leaf = rfl((uint32_t)__popcll(__ballot(at_leaf))); // (scalar registers: the comparison is an s_cmp)
+// The masks and their counts come from the wave's StepMasks: one set per step, taken behind the step, serves the next vote, the step loop's
+// exit test and the retire / refill bookkeeping of extend_segment / connect_segment.  The counts are s_bcnt1 results and every comparison an s_cmp.
+// A mask's lane count as a 32-bit value in a scalar register.  (Left to itself the compiler knows two such counts as 64-bit population counts, compares them as
+// such, and a 64-bit ordered compare exists on the vector unit only: v_mov_b32 + v_cmp_lt_u64 for two s_bcnt1 results.  The empty asm hands it a plain SGPR.)
+__device__ inline uint32_t mask_count(unsigned long long m) { uint32_t n = (uint32_t)__builtin_popcountll(m); asm("" : "+s"(n)); return n; }
+struct StepMasks { unsigned long long node, leaf; uint32_t n_node, n_leaf; }; // lanes whose next step is a node visit / a triangle test, and how many; every other lane is idle or through its ray
+__device__ inline StepMasks step_masks(uint32_t r_cur) { // leaf references have bit 31 set; lanes without a ray hold REF_NONE = -1
+    StepMasks m; m.node = __builtin_amdgcn_ballot_w64((int32_t)r_cur >= 0); m.leaf = __builtin_amdgcn_ballot_w64((int32_t)r_cur < -1);
+    m.n_node = mask_count(m.node); m.n_leaf = mask_count(m.leaf);
+    return m;
+}
+__device__ inline uint32_t n_stepping(const StepMasks &m) { return m.n_node + m.n_leaf; }
+// The step loop of a voting wave as ONE scalar comparison: it goes on while more lanes have a step left than step_floor says.  The loop's rule is "some lane has
+// a step left, and the segment has no ray left to take or fewer than `thresh` lanes are idle or through"; the waves of these kernels are whole (BLOCK is a multiple
+// of 64, and nothing ahead of the loop diverges), so idle-or-through = 64 - n_stepping, and the rule reads n_stepping > 0 (segment exhausted, or thresh >= 64) or
+// n_stepping > 64 - thresh.
+__device__ inline uint32_t step_floor(bool exhausted, uint32_t thresh) { return (exhausted || thresh >= 64u) ? 0u : 64u - thresh; }
+__device__ inline unsigned long long lanes_stepping(const StepMasks &m) { return m.node | m.leaf; } // "the lane holds a ray with a step left"
+__device__ inline uint32_t lanes_not_stepping(const StepMasks &m) { return (uint32_t)__builtin_popcountll(~lanes_stepping(m) & __builtin_amdgcn_ballot_w64(true)); } // idle or finished lanes of the wave
+// Which kernels take the mask form: those without image textures, environment map, normal maps and alpha masks.  The full-feature kernels run at their register
+// cap (96 or 80, with spills), and there the masks' scalar registers cost a spilled vector register (k_extend_rf<3,8,false,0,true>: scratch 0 -> 16 B per lane,
+// k_extend_rf<15,8,true,640,true>: 144 -> 160) and more scalar instructions than they save (classroom, SQ_INSTS_SALU +6 % in both kernels at equal time): they
+// compile the boolean form -- ballots of the booleans, the vote and the loop's tests from `has` and r_cur -- and never touch their StepMasks (which start as
+// zeros, not as a ballot: even a dead one at the head of a segment moved k_extend_rf<15,8,true,640,true>'s spills).
+template <int FEAT> struct StepForm { enum : bool { MASKS = FEAT == FEAT_SIMPLE }; };
+template <bool MASKS>
+__device__ inline bool vote_node_phase(uint32_t r_cur, const StepMasks &m, bool &at_node, bool &at_leaf) {
+    if (MASKS) { at_node = __builtin_amdgcn_inverse_ballot_w64(m.node); at_leaf = __builtin_amdgcn_inverse_ballot_w64(m.leaf); return m.n_node >= m.n_leaf; }
+    at_node = (int32_t)r_cur >= 0; at_leaf = (int32_t)r_cur < -1;
+    const uint32_t n_node = rfl((uint32_t)__popcll(__ballot(at_node))), n_leaf = rfl((uint32_t)__popcll(__ballot(at_leaf)));
     return n_node >= n_leaf;
 }
 // rf_step for the LDS form (vote: the phase most lanes are in, one visit or one triangle; else descend to a leaf, then its triangles)
-template <bool VOTE, bool ALPHA, class Stack>
+template <bool VOTE, bool ALPHA, bool MASKS, class Stack>
 __device__ inline void lf_step(const DScene &sc, uint32_t &r_cur, f3 l_o, f3 l_inv, f3 l_op, float l_sx, float l_sy, float l_sz, uint32_t l_ox, uint32_t l_oy, uint32_t l_oz, uint32_t l_neg, uint32_t l_tri,
-                               float &r_tmax, HitRec &r_h, bool &r_hit, Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n) {
+                               float &r_tmax, HitRec &r_h, bool &r_hit, Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n, StepMasks &sm) {
     if (VOTE) {
         bool at_node, at_leaf;
-        if (vote_node_phase(r_cur, at_node, at_leaf)) {
-            if (at_node) { PT_COUNT_NODE(sc_n) lf_node_visit(r_cur, l_o, l_inv, l_ox, l_oy, l_oz, l_neg, r_tmax, stk, nn); }
+        if (vote_node_phase<MASKS>(r_cur, sm, at_node, at_leaf)) {
+            if (at_node) { PT_COUNT_NODE(sc_n) lf_node_visit<MASKS>(r_cur, l_o, l_inv, l_ox, l_oy, l_oz, l_neg, r_tmax, stk, nn); }
         } else if (at_leaf) {
             PT_COUNT_TRI(sc_n, 1u)
             const bool done = lf_leaf_step<ALPHA>(sc, r_cur, l_op, l_sx, l_sy, l_sz, l_tri, r_tmax, r_h, r_hit, nt, any_rt);
             if (done) r_cur = REF_NONE; else if (r_cur == REF_NONE) r_cur = pop_next_ref<false>(stk, r_tmax);
         }
+        if (MASKS) sm = step_masks(r_cur);
         return;
     }
-    while (r_cur != REF_NONE && !(r_cur & REF_LEAF)) { PT_COUNT_NODE(sc_n) lf_node_visit(r_cur, l_o, l_inv, l_ox, l_oy, l_oz, l_neg, r_tmax, stk, nn); }
+    while (r_cur != REF_NONE && !(r_cur & REF_LEAF)) { PT_COUNT_NODE(sc_n) lf_node_visit<MASKS>(r_cur, l_o, l_inv, l_ox, l_oy, l_oz, l_neg, r_tmax, stk, nn); }
     if (r_cur != REF_NONE) {
         bool done = false;
         while (!done && r_cur != REF_NONE) { PT_COUNT_TRI(sc_n, 1u) done = lf_leaf_step<ALPHA>(sc, r_cur, l_op, l_sx, l_sy, l_sz, l_tri, r_tmax, r_h, r_hit, nt, any_rt); }
         r_cur = done ? REF_NONE : pop_next_ref<false>(stk, r_tmax);
     }
+    if (MASKS) sm = step_masks(r_cur);
 }
 
 __device__ inline GeomTop stage_top(const DScene &sc, v4 *lds, bool top) {
@@ -422,18 +462,19 @@ __device__ inline GeomTop stage_top(const DScene &sc, v4 *lds, bool top) {
                 r_neg[0] = r_inv.x < 0.0f; r_neg[1] = r_inv.y < 0.0f; r_neg[2] = r_inv.z < 0.0f; r_nb3 = neg_bits3(r_neg); r_px = quad_near_x(r_neg); r_py = quad_near_y(r_neg); r_pz = quad_near_z(r_neg); r_shear = ray_shear_inv(d_, r_inv); \
                 r_h.prim = -1; r_h.t = r_tmax; r_h.b0 = r_h.b1 = r_h.b2 = 0.0f; r_h.flags = 0; r_hit = false; r_cur = 0; }
 
-template <bool VOTE, bool QUAD, bool ALPHA, class Stack, class Geom>
+template <bool VOTE, bool QUAD, bool ALPHA, bool MASKS, class Stack, class Geom>
 __device__ inline void rf_step(const Geom &G, const DScene &sc, uint32_t &r_cur, f3 r_o, f3 r_inv, const bool r_neg[3], uint32_t r_nb3, uint32_t r_px, uint32_t r_py, uint32_t r_pz, const RayShear &r_shear, float &r_tmax, HitRec &r_h, bool &r_hit,
-                               Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n) {
+                               Stack &stk, uint32_t &nn, uint32_t &nt, bool any_rt, StepCount &sc_n, StepMasks &sm) {
     if (VOTE) {
         bool at_node, at_leaf;
-        if (vote_node_phase(r_cur, at_node, at_leaf)) {
+        if (vote_node_phase<MASKS>(r_cur, sm, at_node, at_leaf)) {
             if (at_node) { PT_COUNT_NODE(sc_n) node_visit<QUAD, false>(G, r_cur, r_o, r_inv, r_neg, r_tmax, stk, nn, r_nb3, r_px, r_py, r_pz); }
         } else if (at_leaf) {
             PT_COUNT_TRI(sc_n, 1u)
             const bool done = leaf_step<ALPHA>(G, sc, r_cur, r_o, r_shear, r_tmax, r_h, r_hit, nt, any_rt);
             if (done) r_cur = REF_NONE; else if (r_cur == REF_NONE) r_cur = pop_next_ref<false>(stk, r_tmax);
         }
+        if (MASKS) sm = step_masks(r_cur);
         return;
     }
     while (r_cur != REF_NONE && !(r_cur & REF_LEAF)) { PT_COUNT_NODE(sc_n) node_visit<QUAD, false>(G, r_cur, r_o, r_inv, r_neg, r_tmax, stk, nn, r_nb3, r_px, r_py, r_pz); }
@@ -443,6 +484,7 @@ __device__ inline void rf_step(const Geom &G, const DScene &sc, uint32_t &r_cur,
 #endif
         const bool done = leaf_test<false, ALPHA>(G, sc, r_cur, r_o, r_shear, r_tmax, r_h, r_hit, nt, any_rt); r_cur = done ? REF_NONE : pop_next_ref<false>(stk, r_tmax);
     }
+    if (MASKS) sm = step_masks(r_cur);
 }
 
 __device__ inline uint32_t sample_row_of(const DParams &R, uint32_t pid) { // the row of the sample grid a path slot belongs to (path_coord's sy)
@@ -533,13 +575,15 @@ __device__ inline void extend_segment(const DParams &R, const DScene &sc, const 
     bool has = false;    // the lane holds an unfinished ray
     uint32_t e = 0;      // its position
     RF_DECL LF_DECL // (per segment: nothing of a ray is live across the epilogue; quad-form kernels use the RF set, LDS-form kernels the LF set)
+    constexpr bool MASKS = StepForm<FEAT>::MASKS;
+    StepMasks sm = {0ull, 0ull, 0u, 0u}; // (no lane holds a ray yet.)  Behind the retire block `has` is "r_cur != REF_NONE": the masks say who is idle
     for (;;) {
         if (has && r_cur == REF_NONE) { // retire: the hit record is all that leaves this loop
             u4 v; v.x = hit_pack(r_h.prim, r_h.flags); v.y = f2u(r_h.b0); v.z = f2u(r_h.b1); v.w = f2u(r_h.b2);
             pslot(P.hit, e) = v;
             has = false;
         }
-        const unsigned long long idle = __ballot(!has);
+        const unsigned long long idle = MASKS ? ~lanes_stepping(sm) & __builtin_amdgcn_ballot_w64(true) : __ballot(!has);
         const uint32_t n_idle = (uint32_t)__popcll(idle);
         PT_XS(0)
         if (cursor < n && n_idle >= thresh) {
@@ -552,17 +596,20 @@ __device__ inline void extend_segment(const DParams &R, const DScene &sc, const 
                 stk.clear(); has = true;
             }
             cursor += n_idle;
+            if (MASKS) sm = step_masks(r_cur);
             PT_XS(1)
         }
-        if (!__any(has)) break; // every ray of the segment is retired
+        if (MASKS ? n_stepping(sm) == 0u : !__any(has)) break; // every ray of the segment is retired
+        const uint32_t floor_n = MASKS ? step_floor(cursor >= n, thresh) : 0u;
         do {
             PT_XS_COUNT(6, 1) PT_XS_COUNT(9, __popcll(__ballot(has && r_cur != REF_NONE))) PT_XS_COUNT(11, __popcll(__ballot(has && (int32_t)r_cur >= 0))) // steps until enough lanes are through their rays: only then is there something to retire or refill
-            if (GEOM > 0) lf_step<VOTE, (FEAT & FEAT_ALPHA) != 0>(sc, r_cur, l_o, l_inv, l_op, l_sx, l_sy, l_sz, l_ox, l_oy, l_oz, l_neg, l_tri, r_tmax, r_h, r_hit, stk, nn, nt, false, stepc);
-            else rf_step<VOTE, true, (FEAT & FEAT_ALPHA) != 0>(GG, sc, r_cur, r_o, r_inv, r_neg, r_nb3, r_px, r_py, r_pz, r_shear, r_tmax, r_h, r_hit, stk, nn, nt, false, stepc);
+            if (GEOM > 0) lf_step<VOTE, (FEAT & FEAT_ALPHA) != 0, MASKS>(sc, r_cur, l_o, l_inv, l_op, l_sx, l_sy, l_sz, l_ox, l_oy, l_oz, l_neg, l_tri, r_tmax, r_h, r_hit, stk, nn, nt, false, stepc, sm);
+            else rf_step<VOTE, true, (FEAT & FEAT_ALPHA) != 0, MASKS>(GG, sc, r_cur, r_o, r_inv, r_neg, r_nb3, r_px, r_py, r_pz, r_shear, r_tmax, r_h, r_hit, stk, nn, nt, false, stepc, sm);
         // with phase voting the wave goes back to retiring / refilling only when that pays: enough lanes are through their rays
         // (or never had one) to reach the refill threshold, or no lane has a step left.  (Going back for every single ray costs
         // a store instruction and the refill bookkeeping per ray: more than the steps saved.)
-        } while (VOTE && __any(has && r_cur != REF_NONE) && (cursor >= n || (uint32_t)__popcll(__ballot(!has || r_cur == REF_NONE)) < thresh));
+        // (The test reads the counts the step left behind, which are the next step's vote as well: a lane without a ray holds REF_NONE.)
+        } while (VOTE && (MASKS ? n_stepping(sm) > floor_n : (__any(has && r_cur != REF_NONE) && (cursor >= n || (uint32_t)__popcll(__ballot(!has || r_cur == REF_NONE)) < thresh))));
         PT_XS(2)
     }
     // The segment's epilogue runs here, behind the wave's last ray, unless kinds_mask = 0 leaves it to k_epilogue: the hits it
@@ -610,6 +657,8 @@ __device__ inline void connect_segment(const DScene &sc, const DPaths &P, const 
     uint32_t pid = 0, fl = 0, f = 0;
     f3 pre_l = splat3(0.0f); // NEE_PRE records: the path's radiance WITH the record's contribution (both fetched with the ray, added at once: three registers live across the traversal instead of seven), stored if the ray comes through
     RF_DECL LF_DECL // (per segment: nothing of a ray is live across the resolve)
+    constexpr bool MASKS = StepForm<FEAT>::MASKS;
+    StepMasks sm = {0ull, 0ull, 0u, 0u}; // (see extend_segment.)  Behind the retire block "has && !setup" is "r_cur != REF_NONE"
     for (;;) {
         if (has && r_cur == REF_NONE && !setup) { // the ray in flight is done
             if (shadow_phase) {
@@ -630,7 +679,7 @@ __device__ inline void connect_segment(const DScene &sc, const DPaths &P, const 
         // whose shadow ray is done waits for its MIS ray's setup until the idle and the waiting lanes together reach the refill
         // threshold (or nobody else is working), so that one pass of the setup code serves a batch of lanes, not one or two.
         const unsigned long long idle = __ballot(!has);
-        const bool batch = (uint32_t)__popcll(__ballot(!has || setup)) >= thresh || !__any(has && !setup);
+        const bool batch = MASKS ? (lanes_not_stepping(sm) >= thresh || n_stepping(sm) == 0u) : ((uint32_t)__popcll(__ballot(!has || setup)) >= thresh || !__any(has && !setup));
         if (batch && cursor < n && idle) {
             const uint32_t i = cursor + lanes_below(idle);
             if (!has && i < n) {
@@ -654,11 +703,13 @@ __device__ inline void connect_segment(const DScene &sc, const DPaths &P, const 
             if (GEOM > 0) LF_START(LG, xyz(o), xyz(d), shadow_phase ? PT_SHADOW_TMAX : PT_INF) else RF_START(xyz(o), xyz(d), shadow_phase ? PT_SHADOW_TMAX : PT_INF)
             stk.clear(); setup = false;
         }
+        if (MASKS && batch) sm = step_masks(r_cur); // (wave-uniform: behind the divergent set-up, with every lane of the wave)
         if (!__any(has)) break;
+        const uint32_t floor_n = MASKS ? step_floor(cursor >= n, thresh) : 0u;
         do {
-            if (GEOM > 0) lf_step<VOTE, (FEAT & FEAT_ALPHA) != 0>(sc, r_cur, l_o, l_inv, l_op, l_sx, l_sy, l_sz, l_ox, l_oy, l_oz, l_neg, l_tri, r_tmax, r_h, r_hit, stk, nn, nt, shadow_phase, stepc);
-            else rf_step<VOTE, true, (FEAT & FEAT_ALPHA) != 0>(GG, sc, r_cur, r_o, r_inv, r_neg, r_nb3, r_px, r_py, r_pz, r_shear, r_tmax, r_h, r_hit, stk, nn, nt, shadow_phase, stepc);
-        } while (VOTE && __any(has && r_cur != REF_NONE) && (cursor >= n || (uint32_t)__popcll(__ballot(!has || r_cur == REF_NONE)) < thresh)); // (see k_extend_rf)
+            if (GEOM > 0) lf_step<VOTE, (FEAT & FEAT_ALPHA) != 0, MASKS>(sc, r_cur, l_o, l_inv, l_op, l_sx, l_sy, l_sz, l_ox, l_oy, l_oz, l_neg, l_tri, r_tmax, r_h, r_hit, stk, nn, nt, shadow_phase, stepc, sm);
+            else rf_step<VOTE, true, (FEAT & FEAT_ALPHA) != 0, MASKS>(GG, sc, r_cur, r_o, r_inv, r_neg, r_nb3, r_px, r_py, r_pz, r_shear, r_tmax, r_h, r_hit, stk, nn, nt, shadow_phase, stepc, sm);
+        } while (VOTE && (MASKS ? n_stepping(sm) > floor_n : (__any(has && r_cur != REF_NONE) && (cursor >= n || (uint32_t)__popcll(__ballot(!has || r_cur == REF_NONE)) < thresh)))); // (see extend_segment)
     }
     // records with a MIS ray are resolved behind the wave's last ray (see k_extend_rf's epilogue), unless fused_resolve = 0 leaves them to k_resolve
     if (fused_resolve) { __threadfence_block(); resolve_wave<FEAT>(sc, P, Q, it, seg_cap, Gn, s); }
