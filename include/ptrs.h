@@ -425,6 +425,55 @@ int ptrs_converge_schedule(uint32_t spp, uint32_t min_spp, uint32_t *blocks_out,
 int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
                           PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, PtrsConvergeResult *result_out, PtrsStats *stats);
 
+/* Adaptive sampling: a sample range on SOME of the film's tiles, and a render that stops tile by tile (no counterpart in the reference;
+ * DESIGN.md section 13).  The tiles are those of ptrs_film_error: PTRS_ERROR_TILE x PTRS_ERROR_TILE pixels, origin (0, 0), clipped at
+ * the right and bottom edges, index ty * tiles_x + tx.
+ *
+ * ptrs_render_tiles is ptrs_render_range restricted to the active tiles.  tile_active: tiles_x * tiles_y bytes in HOST memory (both
+ * forms), non-zero = active.
+ *  - A sample pixel with raster pixel (px, py) is active iff a pixel of [px - 2, px + 2] x [py - 2, py + 2] lies in an active tile (the
+ *    active tiles dilated by the filter radius: a sample at p in [px, px + 1) reaches exactly the pixels px - 2 .. px + 2).  Exactly
+ *    the samples [sample_begin, sample_end) of the active sample pixels are traced, each once -- adjacent active tiles share their
+ *    apron.  stats->samples = active sample pixels x (sample_end - sample_begin); the ray counts are those of these paths.
+ *  - Every pixel of an active tile ends with the bits ptrs_render_range leaves there with the same arguments and the same starting
+ *    film -- rgb and weight, film and half film; every pixel of an inactive tile keeps its bits.  (ptrs_render_range's own caveat: a
+ *    pass plan that splits the rows is held to 1e-6, not to bits; sample chunks change no bit.)
+ *  - sample_rgb (may be NULL): the range's entries of the active sample pixels are written and equal ptrs_render_samples'; every other
+ *    entry keeps what the caller put there.
+ *  - All tiles active: ptrs_render_range bit for bit, statistics included except passes and launches.  No tile active: PTRS_OK, no
+ *    device launch, the films untouched, zeroed stats.
+ *  - Refused (PTRS_ERR_INVALID) before the first device call: null arguments, a bad sample range, the half film being the film, a row
+ *    band in params (the tile form renders the whole film).
+ *
+ * ptrs_render_adaptive: ptrs_render_converged's schedule (ptrs_converge_schedule), every block on the tiles still active.  All tiles
+ * are active for block 0; behind every block ptrs_film_error is asked, and a tile that took part in the block and whose error is
+ * < target_error is frozen: never active again, so its pixels and its error stay.  (target_error = 0 freezes nothing.)  The render
+ * stops when no tile is active (converged: every tile's error is below the target) or n = spp.  Arguments are checked like
+ * ptrs_render_converged's, with its messages.  tile_spp_out (may be NULL, tiles_x * tiles_y entries): the samples tile t's pixels hold.
+ * Per check the result carries the samples, the tiles that took part in the block and the largest tile error over ALL tiles.
+ * Tile t of the final film is, bit for bit, tile t of ptrs_render_range(0, tile_spp[t]) on the same starting film; while a tile is
+ * active its error at every check equals its error in the ptrs_render_converged run, so tile_spp[t] is the first schedule point at
+ * which that run's error of tile t is below the target, or spp.  The films stay on the device between the blocks; per check the
+ * summary and the tile records (8 bytes per tile) cross to the host. */
+typedef struct PtrsAdaptiveCheck { uint32_t spp; uint32_t tiles_active; float max_tile_error; } PtrsAdaptiveCheck;
+typedef struct PtrsAdaptiveResult {
+    uint32_t spp_done;   /* the samples of the tiles that were active to the end */
+    uint32_t converged;  /* 1: no tile is active */
+    uint32_t n_checks;
+    uint32_t worst_tile; /* of the last check */
+    uint32_t tiles_x, tiles_y;
+    PtrsAdaptiveCheck history[PTRS_CONVERGE_MAX_CHECKS];
+} PtrsAdaptiveResult;
+int ptrs_render_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                      const uint8_t *tile_active, PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats);
+int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                             const uint8_t *tile_active, void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats);
+int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
+                         PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, uint32_t *tile_spp_out, PtrsAdaptiveResult *result_out, PtrsStats *stats);
+/* The freeze rule (a pure function, no device): next_out[t] = 1 where active[t] is non-zero and tiles[t].error is not < target_error,
+ * else 0 (next_out may be active); *n_active_out = how many stay active. */
+int ptrs_adaptive_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float target_error, const uint8_t *active, uint8_t *next_out, uint32_t *n_active_out);
+
 /* PathIntegrator::render_single_pixel (integrator.rs:505-534): radiance of every sample of one
  * pixel, rgb_out[spp*3]. */
 int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera,

@@ -128,6 +128,15 @@ class PtrsConvergeResult(C.Structure):  # ptrs_render_converged
     _fields_ = [("spp_done", C.c_uint32), ("converged", C.c_uint32), ("n_checks", C.c_uint32), ("worst_tile", C.c_uint32), ("history", PtrsConvergeCheck * PtrsConvergeMaxChecks)]
 
 
+class PtrsAdaptiveCheck(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("tiles_active", C.c_uint32), ("max_tile_error", C.c_float)]
+
+
+class PtrsAdaptiveResult(C.Structure):  # ptrs_render_adaptive
+    _fields_ = [("spp_done", C.c_uint32), ("converged", C.c_uint32), ("n_checks", C.c_uint32), ("worst_tile", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
+                ("history", PtrsAdaptiveCheck * PtrsConvergeMaxChecks)]
+
+
 HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4")])
 FILM_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4")])
 TILE_DTYPE = np.dtype([("error", "<f4"), ("valid", "<u4")])

@@ -110,6 +110,106 @@ __global__ __launch_bounds__(BLOCK) void k_film_error_summary(const PtrsTileErro
     if (t == 0u) { PtrsFilmErrorSummary s; s.max_tile_error = se[0]; s.worst_tile = si[0]; s.valid_pixels = sn[0]; s.tiles_x = tiles_x; s.tiles_y = tiles_y; *out = s; }
 }
 
+// ---- the tile form of a pass (pt_adaptive.h): generate, gather and export for the active film tiles only ------------------
+// k_generate with a mask.  The slots stay those of the dense pass (sample x pixels + pixel) and the 64-slot chunks are dealt to the
+// segments as k_generate deals them, so nothing behind this kernel re-indexes; a lane whose sample pixel is not active (ad_pixel_active:
+// up to four flag bytes) makes no path, and the wave compacts the others into the segment with a ballot (wave_push), so a segment's
+// entries stay consecutive and seg_count gets the true number.  With every tile active the queue is k_generate's, entry for entry.
+__global__ __launch_bounds__(BLOCK) void k_generate_tiles(DParams R, DSampler S, DCamera C, DPaths P, DQueues Q, uint32_t seg_cap, uint32_t G, uint32_t deal,
+                                                          const uint8_t *__restrict__ tile_active, int32_t tiles_x) {
+    const uint32_t lane = threadIdx.x & 63u, s = wave_of_launch();
+    if (s >= G) return;
+    const uint32_t chunks = (R.n_paths + 63u) / 64u;
+    const uint32_t e0 = s * seg_cap;
+    uint32_t n = 0; // wave-uniform
+    auto chunk = [&](uint32_t c) {
+        const uint32_t pid = c * 64u + lane;
+        bool on = false;
+        if (pid < R.n_paths) { const PathCoord pc = path_coord(R, S, pid); on = ad_pixel_active(tile_active, tiles_x, R.W, R.H, pc.px, pc.py); }
+        const uint32_t e = e0 + wave_push(n, on); // (at most 64 per chunk, at most seg_cap / 64 chunks per segment: inside the segment)
+        if (on) { generate_item(R, S, C, P, pid, e); pslot(Q.ext[0], e) = pid; }
+    };
+    if (!deal) {
+        for (uint32_t c = s; c < chunks; c += G) chunk(c);
+    } else { // k_generate's walk by image region
+        const uint32_t npix = (uint32_t)(R.row1 - R.row0) * (uint32_t)R.NX;
+        uint32_t cpp = (npix + 63u) / 64u;
+        if (cpp > chunks) cpp = chunks;
+        if (cpp < 1u) cpp = 1u;
+        const uint32_t nsr = (chunks + cpp - 1u) / cpp, r_last = chunks - (nsr - 1u) * cpp, full = r_last * nsr, cps = seg_cap / 64u;
+        const uint32_t c1 = (s + 1u) * cps < chunks ? (s + 1u) * cps : chunks;
+        for (uint32_t cc = s * cps; cc < c1; ++cc) {
+            uint32_t pc, k;
+            if (cc < full) { pc = cc / nsr; k = cc - pc * nsr; }
+            else { const uint32_t d = cc - full, q = d / (nsr - 1u); pc = r_last + q; k = d - q * (nsr - 1u); }
+            chunk(k * cpp + pc);
+        }
+    }
+    if (lane == 0) *seg_count(Q, 0, Q_EXT, G, s) = n;
+}
+
+// k_film for the active tiles: one workgroup per entry of the list, the tile's origin on the FILM's grid (not y0 + 16 j), clipped to the
+// pass's output rows [y0, y1) at both ends -- a tile of the film's grid can straddle y0 of a row-split pass.  Per pixel the sums are
+// k_film's in k_film's order (k, then dx, then dy): a pixel's order never depended on where its tile begins.  Only slots of active
+// sample pixels are read: an apron entry is staged when it lies within the filter radius of a pixel the tile really has (the tile is
+// clipped at the film's right and bottom edges), and such a sample pixel is active by the dilation rule.
+__global__ __launch_bounds__(BLOCK) void k_film_tiles(DParams R, DSampler S, DPaths P, const float *__restrict__ table, v4 *film, int32_t y0, int32_t y1, int32_t tiles_x,
+                                                      const uint32_t *__restrict__ tile_list) {
+    __shared__ float tab[256];
+    __shared__ v4 s_a[400]; __shared__ float s_lb[400];
+    __shared__ uint32_t s_m[400];
+    const uint32_t t = tile_list[blockIdx.x];
+    const int32_t tx0 = (int32_t)(t % (uint32_t)tiles_x) * CV_TILE, ty0 = (int32_t)(t / (uint32_t)tiles_x) * CV_TILE;
+    if (ty0 >= y1 || ty0 + CV_TILE <= y0) return; // (the whole workgroup: none of the tile's rows is in this pass)
+    tab[threadIdx.x] = table[threadIdx.x];
+    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
+    const FilmTile T{tx0, ty0, lx, ly, tx0 + lx, ty0 + ly, tx0 + lx < R.W && ty0 + ly >= y0 && ty0 + ly < y1, (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly))};
+    const int32_t ax1 = (tx0 + CV_TILE < R.W ? tx0 + CV_TILE : R.W) + 2, ay1 = (ty0 + CV_TILE < R.H ? ty0 + CV_TILE : R.H) + 2; // the apron the tile's own pixels reach, exclusive
+    v4 acc; acc.x = acc.y = acc.z = acc.w = 0.0f;
+    if (T.live) acc = film[(size_t)T.y * (size_t)R.W + (size_t)T.x];
+    const uint32_t npix = (uint32_t)(R.row1 - R.row0) * (uint32_t)R.NX;
+    const uint32_t ns = R.s1 - R.s0;
+    for (uint32_t k = 0; k < ns; ++k) {
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < 400u; e += BLOCK) {
+            float pfx = -1.0e9f, pfy = -1.0e9f, lr = 0.0f, lg = 0.0f, lb = 0.0f;
+            uint32_t pid = 0;
+            const bool reached = tx0 - 2 + (int32_t)(e % 20u) < ax1 && ty0 - 2 + (int32_t)(e / 20u) < ay1;
+            if (film_apron_pid(R, S, T, e, k, npix, pid) && reached) {
+                const f2a pf = pslot(P.pfilm, pid); const v4 Lv = pslot(P.L, pid);
+                pfx = pf.x; pfy = pf.y; lr = Lv.x; lg = Lv.y; lb = Lv.z;
+            }
+            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f;
+            s_m[e] = film_footprint_mask(pdx, pdy, T);
+            v4 a; a.x = pdx; a.y = pdy; a.z = lr; a.w = lg; s_a[e] = a; s_lb[e] = lb;
+        }
+        __syncthreads();
+        if (T.live) {
+            for (int32_t dx = 0; dx < 5; ++dx)
+                for (int32_t dy = 0; dy < 5; ++dy) {
+                    const int32_t e = (T.ly + dy) * 20 + (T.lx + dx);
+                    if ((s_m[e] & T.my_bits) != T.my_bits) continue;
+                    const v4 a = s_a[e];
+                    const float w = film_weight_inside(a.x, a.y, T.x, T.y, tab);
+                    acc.x += a.z * w; acc.y += a.w * w; acc.z += s_lb[e] * w; acc.w += w;
+                }
+        }
+    }
+    if (T.live) film[(size_t)T.y * (size_t)R.W + (size_t)T.x] = acc;
+}
+
+// k_export_samples for the active sample pixels: the entries of the others keep what the caller's buffer held
+__global__ __launch_bounds__(BLOCK) void k_export_samples_tiles(DParams R, DSampler S, DPaths P, float *out, const uint8_t *__restrict__ tile_active, int32_t tiles_x) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t pid = blockIdx.x * BLOCK + threadIdx.x; pid < R.n_paths; pid += stride) {
+        const PathCoord c = path_coord(R, S, pid);
+        if (!ad_pixel_active(tile_active, tiles_x, R.W, R.H, c.px, c.py)) continue;
+        const size_t o = (((size_t)c.sy * (size_t)R.NX + (size_t)c.sx) * S.spp + c.s) * 3;
+        const v4 L = pslot(P.L, pid);
+        out[o] = L.x; out[o + 1] = L.y; out[o + 2] = L.z;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;

@@ -15,8 +15,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
+#include "pt_adaptive.h"
 #include "pt_host_scene.h"
 #include "pt_items.h"
 
@@ -163,7 +166,17 @@ struct RenderJob {
     const int32_t *single_pixel = nullptr;   // render_single_pixel (integrator.rs:505-534): raster (px, py), any pixel of the sample bounds; traces that pixel's spp paths only, no film, samples_out = spp * 3 floats
     uint32_t *row_cost = nullptr;            // NY counters (zeroed by the caller): the BVH queries of every sample row's paths are added; no film
     const uint32_t *sample_range = nullptr;  // host.  ptrs_render_range: {begin, end}, samples [begin, end) of the spp-sample render (null: all of them).  The passes run over the range; the sampler, the sample layout and the ray differentials stay those of the whole render
+    // ptrs_render_tiles (pt_adaptive.h): the render restricted to the active film tiles -- only the sample pixels within the filter radius of
+    // an active tile are traced, only the active tiles are gathered.  Needs a back end with the tile hooks (has_tile_hooks) and the whole film.
+    const uint8_t *tile_active = nullptr;      // tiles_x * tiles_y flag bytes
+    const uint8_t *tile_active_host = nullptr; // host: the same flags, for the counts
+    const uint32_t *tile_list = nullptr;       // the indices of the active tiles, ascending (one film workgroup each)
+    uint32_t n_tile_list = 0;
 };
+
+// A back end that can run the tile form: generate_tiles, film_tiles and export_samples_tiles beside generate, film and export_samples.
+template <class BE, class = void> struct has_tile_hooks : std::false_type {};
+template <class BE> struct has_tile_hooks<BE, std::void_t<decltype(std::declval<BE &>().generate_tiles((const uint8_t *)nullptr, (int32_t)0))>> : std::true_type {};
 
 inline DCamera make_camera(const PtrsCamera &cam) {
     DCamera C;
@@ -217,6 +230,10 @@ int render_setup(BE &be, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRe
     u.rb = prm.row_begin; u.re = prm.row_end;
     if (u.re <= u.rb) { u.rb = 0; u.re = prm.height; }
     if (u.rb < 0 || u.re > prm.height) { err = "row band outside the film"; return PTRS_ERR_INVALID; }
+    if (job.tile_active) {
+        if (u.rb != 0 || u.re != prm.height) { err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+        if (!job.tile_active_host || !job.tile_list || job.single_pixel || job.row_cost || job.dump || job.progress) { err = "render_tiles: tile flags without their host copy and list, or with a request the tile form does not serve"; return PTRS_ERR_INVALID; }
+    }
     u.srow0 = std::max(u.rb, 0); u.srow1 = std::min(u.re + 4, g.NY);
     if (job.single_pixel) {
         const int32_t sx = job.single_pixel[0] - g.min_x, sy = job.single_pixel[1] - g.min_y;
@@ -284,7 +301,24 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     // processes on one MI355X measured +18 % over one).  Film kernels are chained in pass order, so the film is formed
     // by exactly the same additions as with a single pipeline.
     const uint64_t band_rows = (uint64_t)(srow1 - srow0);
-    const uint32_t n_lanes = std::max(1u, be.lanes(band_rows * (uint64_t)g.NX * (uint64_t)ns, kinds_present, job.single_pixel != nullptr, ns)); // (the back end may choose by the size of the job: a range's job is its own samples)
+    // The tile form: the slots of a pass stay those of the dense pass (sample x pixels + pixel), so the plan is the dense one; what is
+    // traced, counted and sized by are the ACTIVE sample pixels of its rows.
+    constexpr bool tile_hooks = has_tile_hooks<BE>::value;
+    const bool tiled = job.tile_active != nullptr;
+    if (tiled && !tile_hooks) { err = "this back end has no tile form"; return PTRS_ERR_UNSUPPORTED; }
+    const int32_t tiles_x = ad_tiles_x(prm.width);
+    std::vector<uint32_t> row_active;
+    uint64_t job_pixels = band_rows * (uint64_t)g.NX;
+    if (tiled) {
+        ad_row_counts(job.tile_active_host, prm.width, prm.height, g.min_x, g.min_y, g.NX, g.NY, row_active);
+        job_pixels = 0;
+        for (int32_t r = srow0; r < srow1; ++r) job_pixels += row_active[(size_t)r];
+        if (job_pixels == 0) { // no tile is active: nothing to trace, nothing to gather, no device call
+            if (job.stats) std::memset(job.stats, 0, sizeof(*job.stats));
+            return PTRS_OK;
+        }
+    }
+    const uint32_t n_lanes = std::max(1u, be.lanes(job_pixels * (uint64_t)ns, kinds_present, job.single_pixel != nullptr, ns)); // (the back end may choose by the size of the job: a range's job is its own samples)
     // up to 2^27 paths (~35 GB of path state) per lane: HBM (288 GB) is plentiful, launches and tails are not free.  The back
     // end bounds it by its share of the memory that is free right now, so the library stays embeddable beside other users.
     uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, kinds_present)); // (2^27: a path slot is 27 bits of a NEE-queue entry, pt_scene.h)
@@ -304,7 +338,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     std::memset(&st, 0, sizeof(st));
     std::vector<uint32_t> counts((size_t)(max_iters + 1u) * Q_STRIDE);
     const uint32_t n_passes_total = (uint32_t)(((band_rows + rows_per_pass - 1) / rows_per_pass) * ((ns + samples_per_pass - 1) / samples_per_pass));
-    struct Pending { bool active = false, open = false; uint32_t it = 0, n_paths = 0, pass_no = 0; int32_t y0 = 0, y1 = 0; };
+    struct Pending { bool active = false, open = false, learn = true; uint32_t it = 0, n_paths = 0, pass_no = 0; int32_t y0 = 0, y1 = 0; };
     std::vector<Pending> pending(n_lanes);
     bool null_skip_overrun = false;
     auto round = [&](uint32_t i) {
@@ -329,6 +363,15 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             if (it == max_iters && be.read_count(it, Q_EXT) != 0) null_skip_overrun = true; // paths still alive: never dropped silently
         }
         pd.it = it;
+        if constexpr (tile_hooks) {
+            if (tiled) { // (the gathers of the active tiles, clipped to the pass's output rows; the export of the active sample pixels)
+                if (pd.y1 > pd.y0 && job.film) be.film_tiles(job.film, pd.y0, pd.y1, job.tile_list, job.n_tile_list, tiles_x);
+                if (pd.y1 > pd.y0 && job.film_half) be.film_tiles(job.film_half, pd.y0, pd.y1, job.tile_list, job.n_tile_list, tiles_x);
+                if (job.samples_out) be.export_samples_tiles(job.samples_out, job.tile_active, tiles_x);
+                pd.open = false;
+                return;
+            }
+        }
         if (pd.y1 > pd.y0 && job.film) be.film(job.film, pd.y0, pd.y1); // ordered after the previous pass's film kernel, whichever lane ran it
         if (pd.y1 > pd.y0 && job.film_half) be.film(job.film_half, pd.y0, pd.y1); // (the same pass into the half film: its own running sums, in the same order)
         if (job.samples_out) be.export_samples(job.samples_out);
@@ -340,7 +383,7 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
         close_pass(lane);
         be.select(lane);
         be.read_counts(counts.data(), pd.it + 1u);
-        be.learn(counts.data(), std::min(pd.it + 1u, max_iters + 1u), pd.n_paths); // (gfx950: the scene's survival profile, which places the next passes' hand-over to the fused tail)
+        if (pd.learn) be.learn(counts.data(), std::min(pd.it + 1u, max_iters + 1u), pd.n_paths); // (gfx950: the scene's survival profile, which places the next passes' hand-over to the fused tail)
         for (uint32_t i = 0; i <= pd.it && i < max_iters + 1u; ++i) {
             st.rays_extension += counts[(size_t)i * Q_STRIDE + Q_EXT];
             st.rays_shadow += counts[(size_t)i * Q_STRIDE + Q_SHADOW];
@@ -357,6 +400,9 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     uint32_t pass_no = 0;
     for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass) {
         const int32_t r1 = std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass);
+        uint64_t pass_pixels = (uint64_t)(r1 - r0) * (uint64_t)g.NX;
+        if (tiled) { pass_pixels = 0; for (int32_t r = r0; r < r1; ++r) pass_pixels += row_active[(size_t)r]; }
+        if (pass_pixels == 0) continue; // (tile form: a pass whose sample rows hold no active sample pixel is skipped and not counted)
         for (uint32_t s0 = sb; s0 < se; s0 += (uint32_t)samples_per_pass, ++pass_no) {
             const uint32_t s1 = (uint32_t)std::min<uint64_t>(se, (uint64_t)s0 + samples_per_pass);
             const uint32_t lane = pass_no % n_lanes;
@@ -367,8 +413,12 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             R.row0 = r0; R.row1 = r1; R.s0 = s0; R.s1 = s1;
             R.n_paths = (uint32_t)(r1 - r0) * (uint32_t)g.NX * (s1 - s0);
             if (job.single_pixel) { R.pixel_mode = 1; R.pix_sx = job.single_pixel[0] - g.min_x; R.pix_sy = job.single_pixel[1] - g.min_y; R.n_paths = s1 - s0; }
+            // the paths the pass traces: every slot, or in the tile form those of its active sample pixels (the statistics, the hand-over
+            // to the tail and the survival profile go by these)
+            const uint32_t n_traced = tiled ? (uint32_t)(pass_pixels * (uint64_t)(s1 - s0)) : R.n_paths;
             be.pass_begin(R);
-            be.generate();
+            if constexpr (tile_hooks) { if (tiled) be.generate_tiles(job.tile_active, tiles_x); else be.generate(); }
+            else be.generate();
             uint32_t it = 0;
             if (job.dump) { // (test / bench hook: nothing is rendered beyond the rounds before the dump)
                 for (; it < job.dump->round && it < max_iters; ++it) round(it);
@@ -381,12 +431,13 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
             // expects at most a wave's worth of paths per segment) ONE launch in which every wave takes its segment through all remaining
             // rounds.  Scenes with null-BSDF skips keep the round-by-round form (their passes stay open for more rounds).
             const uint32_t n_rounds = std::min(fixed_iters + spare_rounds, max_iters);
-            const uint32_t tail_from = spare_rounds ? 0xffffffffu : be.tail_round(R.n_paths, n_rounds);
+            const uint32_t tail_from = spare_rounds ? 0xffffffffu : be.tail_round(n_traced, n_rounds);
             for (; it < n_rounds && it < tail_from; ++it) round(it);
             if (it < n_rounds) { be.tail(it, n_rounds); it = n_rounds; }
             // output rows touched by sample rows [r0, r1): pixel row = min_y + sample row, +-2
             const int32_t y0 = std::max(rb, g.min_y + r0 - 2), y1 = std::min(re, g.min_y + r1 - 1 + 2 + 1);
-            pending[lane].active = true; pending[lane].it = it; pending[lane].n_paths = R.n_paths; pending[lane].pass_no = pass_no;
+            pending[lane].active = true; pending[lane].it = it; pending[lane].n_paths = n_traced; pending[lane].pass_no = pass_no;
+            pending[lane].learn = n_traced == R.n_paths; // (a masked pass speaks for its tiles, not for the scene: the survival profile is left alone)
             pending[lane].y0 = (job.single_pixel || y1 <= y0) ? 0 : y0; pending[lane].y1 = (job.single_pixel || y1 <= y0) ? 0 : y1;
             pending[lane].open = true;
             if (!spare_rounds) close_pass(lane); // nothing to ask: the film kernel follows the rounds at once

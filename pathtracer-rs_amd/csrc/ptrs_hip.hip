@@ -1495,6 +1495,7 @@ struct PtrsScene {
     DevBuf counts[MAX_LANES], totals[MAX_LANES], tickets[MAX_LANES];
     DevBuf stats, table, film_tmp, samples_tmp, strat1, strat2, row_cost;
     DevBuf half_tmp, cv_tiles, cv_summary; // ptrs_render_range / ptrs_render_converged: the half film, the tile records and the summary of the error checks
+    DevBuf ad_flags, ad_list;              // ptrs_render_tiles / ptrs_render_adaptive: the tile flags and the list of the active tiles
     DevBuf aov_film_tmp[AOV_PLANES], aov_samples_tmp; // ptrs_render_aov: the host planes' device copies, the per-sample export
     DevBuf aov_band[4], aov_band_pfilm;               // ptrs_render_aov in band mode (pt_aov.h): the values and p_film of one sample index of the whole band
     hipStream_t lane_stream[MAX_LANES] = {}; // lane 0 runs on the caller's stream, the others on these
@@ -2023,6 +2024,18 @@ struct HipBackend {
     }
     void export_aov(float *out, uint32_t off) { t0(T_FILM); hipLaunchKernelGGL(k_export_aov, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, aov_arrays(false), off, out); t1(); }
     void export_samples(float *out) { t0(T_FILM); hipLaunchKernelGGL(k_export_samples, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, P, out); t1(); }
+    // ---- the tile form (pt_adaptive.h; render_impl calls these instead of generate / film / export_samples when the job has tile flags)
+    void generate_tiles(const uint8_t *tile_active, int32_t tiles_x) {
+        t0(T_AUX); hipLaunchKernelGGL(k_generate_tiles, dim3((G + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream, R, S, C, P, Q, seg_cap, G, (uint32_t)deal_by_region(), tile_active, tiles_x); t1();
+    }
+    void film_tiles(v4 *film_px, int32_t y0, int32_t y1, const uint32_t *tile_list, uint32_t n_list, int32_t tiles_x) {
+        if (n_lanes > 1 && film_prev) (void)hipStreamWaitEvent(stream, film_prev, 0); // pass order, whichever lane (film())
+        t0(T_FILM); hipLaunchKernelGGL(k_film_tiles, dim3(n_list), dim3(BLOCK), 0, stream, R, S, P, (const float *)ps->table.p, film_px, y0, y1, tiles_x, tile_list); t1();
+        if (n_lanes > 1) { film_prev = ps->lane_ev[cur]; (void)hipEventRecord(film_prev, stream); }
+    }
+    void export_samples_tiles(float *out, const uint8_t *tile_active, int32_t tiles_x) {
+        t0(T_FILM); hipLaunchKernelGGL(k_export_samples_tiles, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, P, out, tile_active, tiles_x); t1();
+    }
     void end(PtrsStats &st) {
         for (uint32_t l = 0; l < n_lanes; ++l) { select(l); if (hipStreamSynchronize(stream) != hipSuccess) rc = PTRS_ERR_DEVICE; }
         select(0);
@@ -2123,6 +2136,33 @@ int range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRende
     return require_device();
 }
 
+// ptrs_render_tiles / ptrs_render_tiles_device: the checks that need no device, in the style of the range checks, then that there is one
+int tiles_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *tile_active, const void *film, const void *half) {
+    if (!scene || !camera || !params || !film || !tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
+    if (half && half == film) { g_err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
+    if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+    return require_device();
+}
+// The flags (host memory, non-zero = active) into the scene's device copy as 0 / 1, with the list of the active tiles; `job` gets both and
+// the host copy `flags01`.  n_active = 0: nothing was uploaded, the caller has nothing to render.  (A render has drained its streams when it
+// returns, so nothing reads the scene's copies when the next call overwrites them.)
+int upload_tiles(PtrsScene *ps, const PtrsRenderParams &prm, const uint8_t *flags, std::vector<uint8_t> &flags01, HipJob &job, uint32_t &n_active) {
+    const size_t n_tiles = (size_t)ad_tiles_x(prm.width) * (size_t)ad_tiles_y(prm.height);
+    flags01.resize(n_tiles);
+    std::vector<uint32_t> list;
+    for (size_t t = 0; t < n_tiles; ++t) { flags01[t] = flags[t] ? 1 : 0; if (flags[t]) list.push_back((uint32_t)t); }
+    n_active = (uint32_t)list.size();
+    if (list.empty()) return PTRS_OK;
+    int rc;
+    if ((rc = ps->ad_flags.ensure(n_tiles)) != PTRS_OK || (rc = ps->ad_list.ensure(n_tiles * 4)) != PTRS_OK) return rc;
+    HIPCHK(hipMemcpy(ps->ad_flags.p, flags01.data(), n_tiles, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ps->ad_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    job.tile_active = (const uint8_t *)ps->ad_flags.p; job.tile_active_host = flags01.data(); job.tile_list = (const uint32_t *)ps->ad_list.p; job.n_tile_list = n_active;
+    return PTRS_OK;
+}
+
 // ptrs_denoise / ptrs_denoise_device: the checks that need no device
 int dn_check_args(PtrsDenoiser *d, const PtrsDenoiseParams *p, const void *beauty, const void *const *planes, const void *out) {
     if (!d || !p || !beauty || !planes || !out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
@@ -2214,6 +2254,7 @@ int ptrs_abi_sizeof(int which) {
         case 6: return (int)sizeof(PtrsCamera); case 7: return (int)sizeof(PtrsRenderParams); case 8: return (int)sizeof(PtrsStats);
         case 9: return (int)sizeof(PtrsHit); case 10: return (int)sizeof(PtrsFilmPixel); case 11: return (int)sizeof(PtrsDenoiseParams);
         case 12: return (int)sizeof(PtrsTileError); case 13: return (int)sizeof(PtrsFilmErrorSummary); case 14: return (int)sizeof(PtrsConvergeResult);
+        case 15: return (int)sizeof(PtrsAdaptiveCheck); case 16: return (int)sizeof(PtrsAdaptiveResult);
         default: return -1;
     }
 }
@@ -2534,6 +2575,112 @@ int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
         }
         HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
         if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
+        *result_out = res;
+        total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if (stats) *stats = total;
+        return PTRS_OK;
+    });
+}
+
+// ---- adaptive sampling: a sample range on some tiles, render until every tile has converged ---------------------------
+int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
+                             void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = tiles_check_args(scene, camera, params, sample_begin, sample_end, tile_active, film_inout_device, film_half_inout_device);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipSetDevice(scene->device));
+        const uint32_t range[2] = {sample_begin, sample_end};
+        HipJob job;
+        job.film = (v4 *)film_inout_device; job.film_half = (v4 *)film_half_inout_device; job.sample_range = range; job.stream = (hipStream_t)hip_stream; job.stats = stats;
+        std::vector<uint8_t> flags01; uint32_t n_active = 0;
+        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
+        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; } // no tile is active: no launch, the films stay
+        return do_render(scene, camera, params, job);
+    });
+}
+
+int ptrs_render_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
+                      PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = tiles_check_args(scene, camera, params, sample_begin, sample_end, tile_active, film_inout, film_half_inout);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipSetDevice(scene->device));
+        const uint32_t range[2] = {sample_begin, sample_end};
+        HipJob job;
+        job.sample_range = range; job.stats = stats;
+        std::vector<uint8_t> flags01; uint32_t n_active = 0;
+        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
+        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
+        RowBand band;
+        PtrsRenderParams whole = *params; whole.row_begin = 0; whole.row_end = 0;
+        if ((rc = row_band(whole, band)) != PTRS_OK) return rc;
+        return render_host_films(scene, camera, params, band, job, film_inout, film_half_inout, sample_rgb);
+    });
+}
+
+int ptrs_adaptive_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float target_error, const uint8_t *active, uint8_t *next_out, uint32_t *n_active_out) {
+    if (!tiles || !active || !next_out || !n_active_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    *n_active_out = ad_freeze(tiles, n_tiles, target_error, active, next_out);
+    return PTRS_OK;
+}
+
+int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
+                         PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, uint32_t *tile_spp_out, PtrsAdaptiveResult *result_out, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        // (ptrs_render_converged's checks, with its messages)
+        if (!result_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (!(target_error >= 0.0f && target_error < PT_INF)) { g_err = "render_converged: target_error must be finite and >= 0"; return PTRS_ERR_INVALID; }
+        uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
+        if (!scene || !camera || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+        if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
+        if (params->width > 0 && params->height > 0 && (uint64_t)params->width * (uint64_t)params->height >= (1ull << 31)) { g_err = "film too large for the error measure"; return PTRS_ERR_INVALID; }
+        if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_converged renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+        int rc = range_check_args(scene, camera, params, 0u, min_spp, film_inout, film_half_out);
+        if (rc != PTRS_OK) return rc;
+        const auto t_begin = std::chrono::steady_clock::now();
+        HIPCHK(hipSetDevice(scene->device));
+        const int32_t W = params->width, H = params->height;
+        const size_t bytes = (size_t)W * (size_t)H * sizeof(PtrsFilmPixel);
+        const uint32_t tiles_x = (uint32_t)ad_tiles_x(W), tiles_y = (uint32_t)ad_tiles_y(H), n_tiles = tiles_x * tiles_y;
+        if ((rc = scene->film_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->half_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->cv_tiles.ensure((size_t)n_tiles * sizeof(PtrsTileError))) != PTRS_OK ||
+            (rc = scene->cv_summary.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(scene->film_tmp.p, film_inout, bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(scene->half_tmp.p, 0, bytes));
+        PtrsAdaptiveResult res; std::memset(&res, 0, sizeof(res));
+        res.tiles_x = tiles_x; res.tiles_y = tiles_y;
+        PtrsStats total; std::memset(&total, 0, sizeof(total));
+        std::vector<uint8_t> active(n_tiles, 1), flags01;
+        std::vector<uint32_t> tile_spp(n_tiles, 0u);
+        std::vector<PtrsTileError> records(n_tiles);
+        uint32_t n_active = n_tiles;
+        for (uint32_t k = 0; k < n_blocks && n_active != 0; ++k) {
+            const uint32_t parts[2][2] = {{blocks[3 * k], blocks[3 * k + 1]}, {blocks[3 * k + 1], blocks[3 * k + 2]}};
+            HipJob tiles_job; uint32_t n_up = 0;
+            if ((rc = upload_tiles(scene, *params, active.data(), flags01, tiles_job, n_up)) != PTRS_OK) return rc;
+            for (int h = 0; h < 2; ++h) { // the block's first half into both films, its second half into the film only; both on the block's active tiles
+                PtrsStats st;
+                HipJob job = tiles_job;
+                job.film = (v4 *)scene->film_tmp.p; job.film_half = h == 0 ? (v4 *)scene->half_tmp.p : nullptr; job.sample_range = parts[h]; job.stats = &st;
+                if ((rc = do_render(scene, camera, params, job)) != PTRS_OK) return rc;
+                total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
+                total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
+                total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
+            }
+            for (uint32_t t = 0; t < n_tiles; ++t) if (active[t]) tile_spp[t] = blocks[3 * k + 2];
+            PtrsFilmErrorSummary sum;
+            if ((rc = do_film_error(W, H, (const v4 *)scene->film_tmp.p, (const v4 *)scene->half_tmp.p, (PtrsTileError *)scene->cv_tiles.p, (PtrsFilmErrorSummary *)scene->cv_summary.p, nullptr, &sum)) != PTRS_OK) return rc;
+            HIPCHK(hipMemcpy(records.data(), scene->cv_tiles.p, (size_t)n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost)); // (8 bytes per tile: what the freeze rule reads)
+            total.kernel_launches += 2;
+            res.spp_done = blocks[3 * k + 2];
+            res.history[res.n_checks].spp = res.spp_done; res.history[res.n_checks].tiles_active = n_active; res.history[res.n_checks].max_tile_error = sum.max_tile_error; ++res.n_checks;
+            res.worst_tile = sum.worst_tile;
+            n_active = ad_freeze(records.data(), n_tiles, target_error, active.data(), active.data());
+            res.converged = n_active == 0u ? 1u : 0u;
+        }
+        HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
+        if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
+        if (tile_spp_out) std::memcpy(tile_spp_out, tile_spp.data(), (size_t)n_tiles * 4);
         *result_out = res;
         total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         if (stats) *stats = total;

@@ -5,6 +5,7 @@
 // (one-shot render, then film.to_rgba_image().save(DIR/render.png)).  Wiring follows main.rs:101-126:
 //   import -> SamplerBuilder::new(spp, film.get_sample_bounds()) -> PathIntegrator::new(.., max_depth)
 //   -> preprocess -> render -> save.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +26,7 @@ static bool parse_resolution(const char *s, int &w, int &h) { // main.rs:23-33
 
 int main(int argc, char **argv) {
     std::string scene_path, out_dir, dump_path, dump_full_path, env_map_path;
-    bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false, denoise = false;
+    bool default_lights = false, even_bands = false, preview = false, progress = false, aov = false, denoise = false, adaptive = false;
     int n_gpus = 1;
     double target_error = -1.0; int min_samples = 8; // --target_error: render until the film's error is below it, -s is then the ceiling
     int spp = 1, max_depth = 15, w = 640, h = 480; // DEFAULT_RESOLUTION common/mod.rs:14
@@ -50,16 +51,18 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;                     // next to render.png: denoised.png (ptrs_denoise on the film and the first-hit planes, default parameters)
         else if (a == "--target_error") target_error = std::atof(need("--target_error"));  // render blocks of samples (--min_samples, then doubling, at most -s) until ptrs_film_error's
         else if (a == "--min_samples") min_samples = std::atoi(need("--min_samples"));     // largest tile error is below E (ptrs_render_converged); prints every check and the count it stopped at
+        else if (a == "--adaptive") adaptive = true;                   // with --target_error: every block only on the 16 x 16 tiles still above E (ptrs_render_adaptive); writes samples.png next to render.png
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
         else scene_path = a;
     }
     if (scene_path.empty() || (!have_out && dump_path.empty() && dump_full_path.empty())) {
-        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--target_error E [--min_samples N]] [--headless]\n");
+        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--target_error E [--min_samples N] [--adaptive]] [--headless]\n");
         return 2;
     }
     if (target_error >= 0.0 && (n_gpus > 1 || preview || progress)) { std::fprintf(stderr, "error: --target_error does not combine with --gpus, --preview or --progress\n"); return 2; }
+    if (adaptive && target_error < 0.0) { std::fprintf(stderr, "error: --adaptive needs --target_error\n"); return 2; }
     Camera camera; RenderScene scene; std::string err;
     if (!import_scene(scene_path, w, h, camera, scene, err, default_lights, env_map_path)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     if (!dump_full_path.empty()) { if (!dump_scene_full(dump_full_path, camera, scene)) { std::fprintf(stderr, "error: cannot write %s\n", dump_full_path.c_str()); return 1; } if (!have_out && dump_path.empty()) return 0; }
@@ -82,6 +85,28 @@ int main(int argc, char **argv) {
         for (int d = 0; rc == PTRS_OK && d < n_gpus; ++d) {
             std::fprintf(stderr, "INFO device %d: rows %d..%d, %llu rays\n", d, bands[(size_t)d], bands[(size_t)d + 1], (unsigned long long)(sts[(size_t)d].rays_extension + sts[(size_t)d].rays_shadow + sts[(size_t)d].rays_mis));
             st.samples += sts[(size_t)d].samples; st.rays_extension += sts[(size_t)d].rays_extension; st.rays_shadow += sts[(size_t)d].rays_shadow; st.rays_mis += sts[(size_t)d].rays_mis;
+        }
+    } else if (target_error >= 0.0 && adaptive) {
+        PtrsAdaptiveResult res{};
+        std::vector<uint32_t> tile_spp;
+        rc = integrator.render_adaptive(camera, scene, (float)target_error, (uint32_t)(min_samples < 0 ? 0 : min_samples), res, &tile_spp, &st);
+        if (rc == PTRS_OK) {
+            const uint32_t n_tiles = res.tiles_x * res.tiles_y;
+            for (uint32_t k = 0; k < res.n_checks; ++k) std::fprintf(stderr, "INFO check %u: %u spp, %u of %u tiles active, worst %.6g\n", k + 1, res.history[k].spp, res.history[k].tiles_active, n_tiles, (double)res.history[k].max_tile_error);
+            std::fprintf(stderr, "INFO stopped at %u spp (%s, target %.6g, worst tile %u)\n", res.spp_done, res.converged ? "converged" : "ceiling reached", target_error, res.worst_tile);
+            // samples.png: grey = the tile's samples / the ceiling
+            uint32_t ceiling = 1; while (ceiling < (uint32_t)(spp < 1 ? 1 : spp)) ceiling <<= 1; // (-s rounded up to a power of two, sobol.rs:37)
+            std::vector<uint8_t> img((size_t)camera.film.width * (size_t)camera.film.height * 4);
+            for (int y = 0; y < camera.film.height; ++y)
+                for (int x = 0; x < camera.film.width; ++x) {
+                    const uint32_t n = tile_spp[(size_t)(y / PTRS_ERROR_TILE) * res.tiles_x + (size_t)(x / PTRS_ERROR_TILE)];
+                    const uint8_t g = (uint8_t)((255u * std::min(n, ceiling) + ceiling / 2u) / std::max(ceiling, 1u));
+                    uint8_t *q = &img[((size_t)y * (size_t)camera.film.width + (size_t)x) * 4];
+                    q[0] = q[1] = q[2] = g; q[3] = 255;
+                }
+            if (!write_png_rgba8(out_dir + "/samples.png", camera.film.width, camera.film.height, img, err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+            std::fprintf(stderr, "INFO wrote %s/samples.png\n", out_dir.c_str());
+            integrator.set_samples_per_pixel((int)res.spp_done);
         }
     } else if (target_error >= 0.0) {
         PtrsConvergeResult res{};

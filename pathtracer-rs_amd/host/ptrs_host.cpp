@@ -201,6 +201,24 @@ int PathIntegrator::render_converged(Camera &camera, RenderScene &scene, float t
     if (rc != PTRS_OK) last_error = ptrs_last_error();
     return rc;
 }
+int PathIntegrator::render_adaptive(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsAdaptiveResult &result, std::vector<uint32_t> *tile_spp, PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    const PtrsRenderParams p = params(camera);
+    if (tile_spp) tile_spp->assign((size_t)((p.width + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE) * (size_t)((p.height + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE), 0u);
+    rc = ptrs_render_adaptive(gpu_scene_, &camera.abi, &p, target_error, min_spp, camera.film.pixels.data(), nullptr, tile_spp ? tile_spp->data() : nullptr, &result, stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
+int PathIntegrator::render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    const PtrsRenderParams p = params(camera);
+    if (tile_active.size() != (size_t)((p.width + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE) * (size_t)((p.height + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE)) { last_error = "render_tiles: one flag per 16 x 16 tile"; return PTRS_ERR_INVALID; }
+    rc = ptrs_render_tiles(gpu_scene_, &camera.abi, &p, sample_begin, sample_end, tile_active.data(), camera.film.pixels.data(), nullptr, nullptr, stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
 
 bool probe_row_cost(PtrsScene *scene, const PtrsCamera &camera, const PtrsRenderParams &params, int /* strips: the old form's; ignored */, std::vector<float> &row_cost, std::string &err) {
     row_cost.assign((size_t)params.height, 0.0f);

@@ -103,6 +103,11 @@ public:
     // ptrs_film_error's max_tile_error is below target_error.  result: the count it stopped at, whether the last check
     // was below the target, and (spp, error) of every check.  The film is bit-identical to a render of result.spp_done samples' range.
     int render_converged(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsConvergeResult &result, PtrsStats *stats = nullptr);
+    // ptrs_render_adaptive: the same schedule, every block on the 16 x 16 tiles whose error has not been below target_error yet.
+    // tile_spp (may be null): tiles_x * tiles_y entries, the samples each tile's pixels hold.
+    int render_adaptive(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsAdaptiveResult &result, std::vector<uint32_t> *tile_spp = nullptr, PtrsStats *stats = nullptr);
+    // ptrs_render_tiles: samples [sample_begin, sample_end) on the active tiles (tiles_x * tiles_y flag bytes) into camera.film
+    int render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats = nullptr);
     // another sample count for the renders that follow (the planes of render_aov at the count render_converged stopped at)
     void set_samples_per_pixel(int spp) { sb_ = SamplerBuilder(spp, sb_.sample_bounds); }
     // When set, render() publishes the film after every pass of the pipeline (ptrs_render_progressive) and calls this with

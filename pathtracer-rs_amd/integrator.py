@@ -46,7 +46,7 @@ def load_library():
             raise PtrsError("ABI struct %s: library %d bytes, binding %d bytes" % (s.__name__, L.ptrs_abi_sizeof(i), C.sizeof(s)))
     if L.ptrs_abi_sizeof(11) != C.sizeof(abi.PtrsDenoiseParams):
         raise PtrsError("ABI struct PtrsDenoiseParams: library %d bytes, binding %d bytes" % (L.ptrs_abi_sizeof(11), C.sizeof(abi.PtrsDenoiseParams)))
-    for i, s in ((12, abi.PtrsTileError), (13, abi.PtrsFilmErrorSummary), (14, abi.PtrsConvergeResult)):
+    for i, s in ((12, abi.PtrsTileError), (13, abi.PtrsFilmErrorSummary), (14, abi.PtrsConvergeResult), (15, abi.PtrsAdaptiveCheck), (16, abi.PtrsAdaptiveResult)):
         if L.ptrs_abi_sizeof(i) != C.sizeof(s):
             raise PtrsError("ABI struct %s: library %d bytes, binding %d bytes" % (s.__name__, L.ptrs_abi_sizeof(i), C.sizeof(s)))
     L.ptrs_render_range.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -55,6 +55,10 @@ def load_library():
     L.ptrs_film_error_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptrs_converge_schedule.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.ptrs_render_converged.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_render_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_render_tiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptrs_adaptive_freeze.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptrs_set_option.argtypes = [C.c_char_p, C.c_int64]
     L.ptrs_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.ptrs_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
@@ -320,6 +324,72 @@ class PathIntegrator:
         self.last_stats = stats
         out = dict(spp_done=int(res.spp_done), converged=bool(res.converged), worst_tile=int(res.worst_tile),
                    history=[(int(res.history[k].spp), float(res.history[k].max_tile_error)) for k in range(res.n_checks)])
+        if want_half:
+            out["half"] = half
+        return out
+
+    def _tile_flags(self, p, tiles, what):
+        T = abi.PtrsErrorTile
+        shape = ((p.height + T - 1) // T, (p.width + T - 1) // T)
+        flags = np.ascontiguousarray(np.asarray(tiles) != 0, dtype=np.uint8)
+        if flags.size != shape[0] * shape[1]:
+            raise PtrsError("%s: tiles must have tiles_y x tiles_x = %d x %d entries" % (what, shape[0], shape[1]))
+        return flags
+
+    def render_tiles(self, camera, scene, sample_begin, sample_end, tiles, half=None, samples=None, flags=0):
+        """ptrs_render_tiles: render_range restricted to the active tiles -- `tiles` is a (tiles_y, tiles_x) array over the 16 x 16
+        tiles of film_error, non-zero = active.  Only the sample pixels within the filter radius of an active tile are traced; the
+        pixels of the active tiles end with render_range's bits, all others keep theirs; of `samples` only the entries of the
+        active sample pixels are written.  Returns the stats (samples = active sample pixels x the range)."""
+        p = self.params(camera, 0, 0, flags)
+        tf = self._tile_flags(p, tiles, "render_tiles")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        film = camera.film.pixels
+        if half is not None and (half.dtype != abi.FILM_DTYPE or half.shape != film.shape or not half.flags.c_contiguous):
+            raise PtrsError("render_tiles: half must be a contiguous (H, W) FILM_DTYPE array")
+        if samples is not None:
+            spp = p.spp if p.sampler == abi.SAMPLER_STRATIFIED else round_up_pow2(p.spp)
+            if samples.dtype != np.float32 or samples.shape != (p.height + 4, p.width + 4, spp, 3) or not samples.flags.c_contiguous:
+                raise PtrsError("render_tiles: samples must be a contiguous (H + 4, W + 4, spp, 3) float32 array")
+        _check(load_library().ptrs_render_tiles(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), tf.ctypes.data, film.ctypes.data,
+                                                half.ctypes.data if half is not None else None, samples.ctypes.data if samples is not None else None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_tiles_device(self, camera, scene, sample_begin, sample_end, tiles, film_device_ptr, half_device_ptr=0, stream=0, flags=0):
+        """Same, the film (and the half film, 0: none) in device memory (width*height*16 bytes each); `tiles` stays a host array."""
+        p = self.params(camera, 0, 0, flags)
+        tf = self._tile_flags(p, tiles, "render_tiles_device")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        _check(load_library().ptrs_render_tiles_device(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), tf.ctypes.data, int(film_device_ptr),
+                                                       int(half_device_ptr) or None, int(stream) or None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_adaptive(self, camera, scene, target_error, min_spp=8, want_half=False):
+        """ptrs_render_adaptive: render_converged's schedule, every block on the tiles whose error has not been below target_error yet
+        (a tile below it is frozen: never rendered again).  Stops when no tile is active or at the sampler's spp.  Returns a dict:
+        spp_done, converged, worst_tile, tile_spp (a (tiles_y, tiles_x) array: the samples each tile's pixels hold), history =
+        [(spp, tiles_active, max_tile_error) per check], and with want_half the half film.  Tile t of the film is tile t of
+        render_range(0, tile_spp[t])."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        res = abi.PtrsAdaptiveResult()
+        film = camera.film.pixels
+        half = np.zeros_like(film) if want_half else None
+        T = abi.PtrsErrorTile
+        tile_spp = np.zeros(((p.height + T - 1) // T, (p.width + T - 1) // T), dtype=np.uint32)
+        _check(load_library().ptrs_render_adaptive(ds.handle, C.addressof(cam), C.addressof(p), float(target_error), int(min_spp), film.ctypes.data,
+                                                   half.ctypes.data if want_half else None, tile_spp.ctypes.data, C.addressof(res), C.addressof(stats)))
+        self.last_stats = stats
+        out = dict(spp_done=int(res.spp_done), converged=bool(res.converged), worst_tile=int(res.worst_tile), tile_spp=tile_spp,
+                   history=[(int(res.history[k].spp), int(res.history[k].tiles_active), float(res.history[k].max_tile_error)) for k in range(res.n_checks)])
         if want_half:
             out["half"] = half
         return out
