@@ -474,6 +474,45 @@ int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsR
  * else 0 (next_out may be active); *n_active_out = how many stay active. */
 int ptrs_adaptive_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float target_error, const uint8_t *active, uint8_t *next_out, uint32_t *n_active_out);
 
+/* Feature planes for sample ranges and tiles, and the planes of an adaptive film (no counterpart in the reference; DESIGN.md section
+ * 14).  planes / planes_inout / sample_aov as in ptrs_render_aov; every _device form takes the planes (and sample_aov) in device memory
+ * and a stream; tile_active and tile_spp are HOST memory in both forms.
+ *
+ * ptrs_render_aov_range: samples [sample_begin, sample_end) of `params`' AOV call, accumulated into the planes.  params->spp stays the
+ * whole render's count (the differential scale 1 / sqrt(spp) is the whole render's).  sample_aov has ptrs_render_aov's layout with the
+ * absolute sample number; only the range's entries are written.  Ranges that tile [0, spp) in order, from the same starting planes, give
+ * ptrs_render_aov's planes and samples bit for bit under every pass plan.  Refused (PTRS_ERR_INVALID) before the first device call, with
+ * ptrs_render_range's messages, unless sample_begin < sample_end <= the rounded spp.
+ *
+ * ptrs_render_aov_tiles: the range form restricted to the active tiles under ptrs_render_tiles' rules -- the same dilation rule;
+ * exactly the range's samples of the active sample pixels are traced, each once; every pixel of an active tile ends with the bits
+ * ptrs_render_aov_range leaves there from the same starting planes, every pixel of an inactive tile keeps its bits in every plane
+ * asked for; sample_aov entries of inactive sample pixels keep the caller's values; stats->samples = active sample pixels x
+ * (sample_end - sample_begin).  All tiles active: the range form bit for bit.  No tile active: PTRS_OK, no launch, planes untouched,
+ * zeroed stats.  A row band in params is refused.
+ *
+ * ptrs_render_aov_adaptive: the planes of a film whose tile t holds tile_spp[t] samples of ptrs_converge_schedule(spp, min_spp) -- what
+ * ptrs_render_adaptive returns in tile_spp_out; a pure function of tile_spp, the beauty render is not needed.  Block [begin, end) runs
+ * on the tiles with tile_spp[t] >= end; consecutive blocks with the same tile set run as one range, a block without a tile is skipped.
+ * The planes stay on the device between the blocks.  Plane k's tile t equals tile t of ptrs_render_aov_range(0, tile_spp[t]) bit for
+ * bit; a tile with 0 keeps its bits.  From cleared films, under a pass plan that keeps the band's rows in one pass, every plane's
+ * weight equals the weight of the ptrs_render_adaptive film that produced tile_spp, bit for bit on every pixel.  Refused before the
+ * first device call: null arguments, a bad planes mask, a row band, an spp or min_spp the schedule refuses, a tile_spp[t] that is
+ * neither 0 nor the end of a block (the message names the tile).  stats are summed over the blocks like ptrs_render_adaptive's. */
+int ptrs_render_aov_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                          uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats);
+int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                                 uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats);
+int ptrs_render_aov_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                          const uint8_t *tile_active, uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats);
+int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
+                                 const uint8_t *tile_active, uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device,
+                                 void *hip_stream, PtrsStats *stats);
+int ptrs_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp,
+                             uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], PtrsStats *stats);
+int ptrs_render_aov_adaptive_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp,
+                                    uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], void *hip_stream, PtrsStats *stats);
+
 /* PathIntegrator::render_single_pixel (integrator.rs:505-534): radiance of every sample of one
  * pixel, rgb_out[spp*3]. */
 int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera,

@@ -4,7 +4,8 @@
 // and weights of the beauty image.  Everything that is needed sits in the pipeline after round 0 -- the hit (triangle id, barycentrics)
 // in P.hit, the film position in P.pfilm -- so an AOV call is a render cut after its first extension: generate, extend(0), then
 //   aov_item          : camera_ray -> tri_surface -> surface_differentials -> the NormalMaterial chain (make_bsdf's order) -> the values
-//   render_aov_impl   : render_impl's set-up, pass plan and lanes around those three stages and the plane films
+//   render_aov_impl   : render_impl's set-up, pass plan and lanes around those three stages and the plane films; a sample range and a
+//                       set of film tiles restrict it like render_impl
 // Specular first hits are not followed: a mirror shows the mirror's own surface.  The reference has no such call.
 #pragma once
 #include "pt_render.h"
@@ -81,27 +82,57 @@ PT_HD void aov_sample_row(const AovRec &a, float *o) {
 // sample index first, leave their values (and p_film) in arrays of the whole band (72 bytes per sample pixel), and when a sample
 // index's last block is through ONE film gather runs over the band -- the order of a whole-band pass: sample, x, y.  On one lane: the
 // stream orders the blocks, the gather and the next sample's blocks.
+//
+// Sample ranges and tiles.  `job` carries RenderJob's sample_range and tile fields, nothing else of it is read.
+// A range runs the passes over [begin, end) and leaves sampler, sample layout and differentials those of the whole render: in either
+// mode a pixel receives its samples sample index by sample index, so ranges that tile [0, spp) in order form the dense call's sums.
+// The tile form keeps the dense pass's slots and plan (render_impl's tile form): generate_tiles makes paths for the active sample
+// pixels only, k_aov walks that queue, the gather runs one workgroup per active tile and reads only slots of active sample pixels --
+// the others hold what earlier passes (or, in band mode, earlier sample indices and calls) left there.  A pass whose rows hold no active
+// sample pixel is skipped; in band mode the gather follows the last block of the sample index that was not.
+template <class BE, class = void> struct has_aov_tile_hooks : std::false_type {};
+template <class BE> struct has_aov_tile_hooks<BE, std::void_t<decltype(std::declval<BE &>().export_aov_tiles((float *)nullptr, 0u, (const uint8_t *)nullptr, (int32_t)0))>> : has_tile_hooks<BE> {};
+
 template <class BE>
 int render_aov_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm_in,
-                    uint32_t planes, const DAovFilm &films /* backend memory, W*H each */, float *samples_out /* backend memory or null */, PtrsStats *stats, std::string &err) {
+                    uint32_t planes, const DAovFilm &films /* backend memory, W*H each */, float *samples_out /* backend memory or null */, PtrsStats *stats, std::string &err,
+                    const RenderJob &job_in = RenderJob{}) {
     using clock = std::chrono::steady_clock;
     auto t_begin = clock::now();
     if (prm_in.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
     PtrsRenderParams prm = prm_in;
     prm.max_depth = 0; // the pass ends behind its first extension: the epilogue buckets nothing
+    RenderJob job; // (what an AOV call can be asked for)
+    job.sample_range = job_in.sample_range; job.tile_active = job_in.tile_active; job.tile_active_host = job_in.tile_active_host; job.tile_list = job_in.tile_list; job.n_tile_list = job_in.n_tile_list;
     RenderSetup u;
-    int rc = render_setup(be, bvh_depth, cam, prm, RenderJob{}, u, err);
+    int rc = render_setup(be, bvh_depth, cam, prm, job, u, err);
     if (rc != PTRS_OK) return rc;
     const SampleGrid &g = u.g;
+    const uint32_t sb = u.sb, se = u.se, ns = se - sb;
     const int32_t rb = u.rb, re = u.re, srow0 = u.srow0, srow1 = u.srow1;
     DParams R = u.R;
 
     const uint64_t band_rows = (uint64_t)(srow1 - srow0);
-    const uint32_t n_lanes = std::max(1u, be.lanes(band_rows * (uint64_t)g.NX * (uint64_t)g.spp, sc_host_feat.kinds_present, false, g.spp));
+    constexpr bool tile_hooks = has_aov_tile_hooks<BE>::value;
+    const bool tiled = job.tile_active != nullptr;
+    if (tiled && !tile_hooks) { err = "this back end has no tile form"; return PTRS_ERR_UNSUPPORTED; }
+    const int32_t tiles_x = ad_tiles_x(prm.width);
+    std::vector<uint32_t> row_active;
+    uint64_t job_pixels = band_rows * (uint64_t)g.NX;
+    if (tiled) { // (render_impl's tile form: what is traced and counted are the active sample pixels of the rows)
+        ad_row_counts(job.tile_active_host, prm.width, prm.height, g.min_x, g.min_y, g.NX, g.NY, row_active);
+        job_pixels = 0;
+        for (int32_t r = srow0; r < srow1; ++r) job_pixels += row_active[(size_t)r];
+        if (job_pixels == 0) { // no tile is active: no device call
+            if (stats) std::memset(stats, 0, sizeof(*stats));
+            return PTRS_OK;
+        }
+    }
+    const uint32_t n_lanes = std::max(1u, be.lanes(job_pixels * (uint64_t)ns, sc_host_feat.kinds_present, false, ns));
     uint64_t capacity = std::min<uint64_t>(1ull << 27, prm.paths_per_pass ? prm.paths_per_pass : be.auto_capacity(n_lanes, sc_host_feat.kinds_present));
     if (capacity < (uint64_t)g.NX) capacity = (uint64_t)g.NX;
     PassPlan pp;
-    if (!plan_passes(band_rows, (uint64_t)g.NX, g.spp, capacity, n_lanes, prm.paths_per_pass != 0, pp)) { err = "pass too large"; return PTRS_ERR_INVALID; }
+    if (!plan_passes(band_rows, (uint64_t)g.NX, ns, capacity, n_lanes, prm.paths_per_pass != 0, pp)) { err = "pass too large"; return PTRS_ERR_INVALID; }
     const uint64_t rows_per_pass = pp.rows_per_pass, samples_per_pass = pp.samples_per_pass;
 
     const uint32_t count_rows = 2u; // round 0, and the row its kernels may look ahead to
@@ -117,14 +148,23 @@ int render_aov_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uin
         if (band_rows * (uint64_t)g.NX > (1ull << 27)) { err = "band too large for the pass capacity"; return PTRS_ERR_UNSUPPORTED; }
         if ((rc = be.aov_band_begin(band_rows * (uint64_t)g.NX, err)) != PTRS_OK) return rc;
     }
-    struct Pass { int32_t r0, r1; uint32_t s0, s1; bool last_block; };
+    struct Pass { int32_t r0, r1; uint32_t s0, s1; bool last_block; uint64_t pixels /* the sample pixels it traces */; };
     std::vector<Pass> plan;
+    auto add_pass = [&](int32_t r0, uint32_t s0, uint32_t s1) {
+        const int32_t r1 = std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass);
+        uint64_t pixels = (uint64_t)(r1 - r0) * (uint64_t)g.NX;
+        if (tiled) { pixels = 0; for (int32_t r = r0; r < r1; ++r) pixels += row_active[(size_t)r]; }
+        if (pixels == 0) return; // (tile form: a pass whose sample rows hold no active sample pixel is skipped and not counted)
+        plan.push_back(Pass{r0, r1, s0, s1, true, pixels});
+    };
     if (band_mode) {
-        for (uint32_t s0 = 0; s0 < g.spp; ++s0)
-            for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass) plan.push_back(Pass{r0, std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass), s0, s0 + 1u, r0 + (int32_t)rows_per_pass >= srow1});
+        for (uint32_t s0 = sb; s0 < se; ++s0) {
+            for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass) add_pass(r0, s0, s0 + 1u);
+            for (size_t i = plan.size(); i-- > 0 && plan[i].s0 == s0;) plan[i].last_block = i + 1 == plan.size(); // the gather follows the sample index's last block
+        }
     } else {
         for (int32_t r0 = srow0; r0 < srow1; r0 += (int32_t)rows_per_pass)
-            for (uint32_t s0 = 0; s0 < g.spp; s0 += (uint32_t)samples_per_pass) plan.push_back(Pass{r0, std::min<int32_t>(srow1, r0 + (int32_t)rows_per_pass), s0, (uint32_t)std::min<uint64_t>(g.spp, (uint64_t)s0 + samples_per_pass), true});
+            for (uint32_t s0 = sb; s0 < se; s0 += (uint32_t)samples_per_pass) add_pass(r0, s0, (uint32_t)std::min<uint64_t>(se, (uint64_t)s0 + samples_per_pass));
     }
     struct Pending { bool active = false; uint32_t n_paths = 0; };
     std::vector<Pending> pending(n_lanes);
@@ -148,20 +188,26 @@ int render_aov_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uin
         R.row0 = ps.r0; R.row1 = ps.r1; R.s0 = ps.s0; R.s1 = ps.s1;
         R.n_paths = (uint32_t)(ps.r1 - ps.r0) * (uint32_t)g.NX * (ps.s1 - ps.s0);
         const uint32_t off = band_mode ? (uint32_t)(ps.r0 - srow0) * (uint32_t)g.NX : 0u; // the pass's first slot in the band's arrays
+        const uint32_t n_traced = tiled ? (uint32_t)(ps.pixels * (uint64_t)(ps.s1 - ps.s0)) : R.n_paths;
         be.pass_begin(R);
-        be.generate();
+        if constexpr (tile_hooks) { if (tiled) be.generate_tiles(job.tile_active, tiles_x); else be.generate(); }
+        else be.generate();
         be.extend(0);
-        be.aov(planes, off);
-        if (samples_out) be.export_aov(samples_out, off);
+        be.aov(planes, off); // (walks round 0's queue: in the tile form only the slots of active sample pixels are written)
+        if (samples_out) {
+            if constexpr (tile_hooks) { if (tiled) be.export_aov_tiles(samples_out, off, job.tile_active, tiles_x); else be.export_aov(samples_out, off); }
+            else be.export_aov(samples_out, off);
+        }
         // output rows touched by the sample rows gathered: pixel row = min_y + sample row, +-2
         const int32_t f0 = band_mode ? srow0 : ps.r0, f1 = band_mode ? srow1 : ps.r1;
         const int32_t y0 = std::max(rb, g.min_y + f0 - 2), y1 = std::min(re, g.min_y + f1 - 1 + 2 + 1);
         if (ps.last_block && y1 > y0) { // ordered after the previous film launches, whichever lane ran them
             DParams Rf = R;
             if (band_mode) { Rf.row0 = srow0; Rf.row1 = srow1; Rf.n_paths = (uint32_t)band_rows * (uint32_t)g.NX; }
-            be.film_aov(planes, films, y0, y1, Rf);
+            if constexpr (tile_hooks) { if (tiled) be.film_aov_tiles(planes, films, y0, y1, Rf, job.tile_list, job.n_tile_list, tiles_x); else be.film_aov(planes, films, y0, y1, Rf); }
+            else be.film_aov(planes, films, y0, y1, Rf);
         }
-        pending[lane].active = true; pending[lane].n_paths = R.n_paths;
+        pending[lane].active = true; pending[lane].n_paths = n_traced;
         ++pass_no;
     }
     st.ms_enqueue = std::chrono::duration<double, std::milli>(clock::now() - t_begin).count();

@@ -210,6 +210,86 @@ __global__ __launch_bounds__(BLOCK) void k_export_samples_tiles(DParams R, DSamp
     }
 }
 
+// ---- the tile form of an AOV pass (pt_aov.h): k_generate_tiles and k_aov as they stand, then these two ----------------------
+// k_film_aov's three-accumulator gather with k_film_tiles' placement: one workgroup per entry of the list, the tile's origin on the film's
+// grid, clipped to [y0, y1), and the `reached` test on every apron entry.  That test is what keeps the kernel off STALE slots: k_aov
+// walks the queue k_generate_tiles made, so the value arrays (and in band mode the band's p_film copy) are written for active sample
+// pixels only; every other slot holds what an earlier pass, sample index or call left there.  An apron entry is read only when it is
+// within the filter radius of a pixel the tile really has, and such a sample pixel is active by the dilation rule (ad_pixel_active).
+// Per pixel the additions are k_film_aov's in its order (k, dx, dy).  LDS as k_film_aov: 3 x 400 x 16 + 400 x 4 + 1024 bytes.
+__global__ __launch_bounds__(BLOCK) void k_film_aov_tiles(DParams R, DSampler S, DPaths P, DAov A, const float *__restrict__ table, DAovFilm F, int32_t y0, int32_t y1, int32_t tiles_x,
+                                                          const uint32_t *__restrict__ tile_list) {
+    __shared__ float tab[256];
+    __shared__ v4 s_p[400], s_al[400], s_n[400]; // p_film.xy - 0.5, depth, coverage | albedo.rgb | normal.rgb
+    __shared__ uint32_t s_m[400];
+    const uint32_t t = tile_list[blockIdx.x];
+    const int32_t tx0 = (int32_t)(t % (uint32_t)tiles_x) * CV_TILE, ty0 = (int32_t)(t / (uint32_t)tiles_x) * CV_TILE;
+    if (ty0 >= y1 || ty0 + CV_TILE <= y0) return; // (the whole workgroup: none of the tile's rows is in this gather)
+    tab[threadIdx.x] = table[threadIdx.x];
+    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
+    const FilmTile T{tx0, ty0, lx, ly, tx0 + lx, ty0 + ly, tx0 + lx < R.W && ty0 + ly >= y0 && ty0 + ly < y1, (1u << (uint32_t)lx) | (1u << (16u + (uint32_t)ly))};
+    const int32_t ax1 = (tx0 + CV_TILE < R.W ? tx0 + CV_TILE : R.W) + 2, ay1 = (ty0 + CV_TILE < R.H ? ty0 + CV_TILE : R.H) + 2; // the apron the tile's own pixels reach, exclusive
+    const bool want_al = F.plane[AOV_ALBEDO] != nullptr, want_n = F.plane[AOV_NORMAL] != nullptr, want_d = F.plane[AOV_DEPTH] != nullptr;
+    const size_t px = (size_t)T.y * (size_t)R.W + (size_t)T.x;
+    v4 acc_al, acc_n, acc_d;
+    acc_al.x = acc_al.y = acc_al.z = acc_al.w = 0.0f; acc_n = acc_al; acc_d = acc_al;
+    if (T.live) {
+        if (want_al) acc_al = F.plane[AOV_ALBEDO][px];
+        if (want_n) acc_n = F.plane[AOV_NORMAL][px];
+        if (want_d) acc_d = F.plane[AOV_DEPTH][px];
+    }
+    const uint32_t npix = (uint32_t)(R.row1 - R.row0) * (uint32_t)R.NX;
+    const uint32_t ns = R.s1 - R.s0;
+    for (uint32_t k = 0; k < ns; ++k) {
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < 400u; e += BLOCK) {
+            float pfx = -1.0e9f, pfy = -1.0e9f;
+            v4 al, nd; al.x = al.y = al.z = al.w = 0.0f; nd = al;
+            uint32_t pid = 0;
+            const bool reached = tx0 - 2 + (int32_t)(e % 20u) < ax1 && ty0 - 2 + (int32_t)(e / 20u) < ay1;
+            if (film_apron_pid(R, S, T, e, k, npix, pid) && reached) {
+                const f2a pf = pslot(P.pfilm, pid);
+                pfx = pf.x; pfy = pf.y; al = pslot(A.albedo, pid); nd = pslot(A.normal, pid);
+            }
+            const float pdx = pfx - 0.5f, pdy = pfy - 0.5f;
+            s_m[e] = film_footprint_mask(pdx, pdy, T);
+            v4 a; a.x = pdx; a.y = pdy; a.z = nd.w; a.w = al.w; s_p[e] = a; s_al[e] = al; s_n[e] = nd;
+        }
+        __syncthreads();
+        if (T.live) {
+            for (int32_t dx = 0; dx < 5; ++dx)
+                for (int32_t dy = 0; dy < 5; ++dy) {
+                    const int32_t e = (T.ly + dy) * 20 + (T.lx + dx);
+                    if ((s_m[e] & T.my_bits) != T.my_bits) continue;
+                    const v4 a = s_p[e];
+                    const float w = film_weight_inside(a.x, a.y, T.x, T.y, tab);
+                    if (want_al) { const v4 c = s_al[e]; acc_al.x += c.x * w; acc_al.y += c.y * w; acc_al.z += c.z * w; acc_al.w += w; }
+                    if (want_n) { const v4 c = s_n[e]; acc_n.x += c.x * w; acc_n.y += c.y * w; acc_n.z += c.z * w; acc_n.w += w; }
+                    if (want_d) { acc_d.x += a.z * w; acc_d.y += a.w * w; acc_d.z += 0.0f * w; acc_d.w += w; }
+                }
+        }
+    }
+    if (T.live) {
+        if (want_al) F.plane[AOV_ALBEDO][px] = acc_al;
+        if (want_n) F.plane[AOV_NORMAL][px] = acc_n;
+        if (want_d) F.plane[AOV_DEPTH][px] = acc_d;
+    }
+}
+
+// k_export_aov for the active sample pixels: the entries of the others keep what the caller's buffer held
+__global__ __launch_bounds__(BLOCK) void k_export_aov_tiles(DParams R, DSampler S, DAov A, uint32_t off, float *out, const uint8_t *__restrict__ tile_active, int32_t tiles_x) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t pid = blockIdx.x * BLOCK + threadIdx.x; pid < R.n_paths; pid += stride) {
+        const PathCoord c = path_coord(R, S, pid);
+        if (!ad_pixel_active(tile_active, tiles_x, R.W, R.H, c.px, c.py)) continue;
+        float *o = out + (((size_t)c.sy * (size_t)R.NX + (size_t)c.sx) * S.spp + c.s) * AOV_SAMPLE_FLOATS;
+        const v4 al = pslot(A.albedo, off + pid), nd = pslot(A.normal, off + pid), pp = pslot(A.pos, off + pid);
+        o[0] = al.x; o[1] = al.y; o[2] = al.z; o[3] = al.w;
+        o[4] = nd.x; o[5] = nd.y; o[6] = nd.z; o[7] = nd.w;
+        o[8] = pp.x; o[9] = pp.y; o[10] = pp.z; o[11] = pp.w;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_sobol(DSampler S, uint32_t n, const int32_t *px, const int32_t *py, const uint64_t *sn, const uint32_t *dims, float *out, uint64_t *idx_out) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;

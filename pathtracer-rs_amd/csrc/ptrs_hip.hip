@@ -2036,6 +2036,29 @@ struct HipBackend {
     void export_samples_tiles(float *out, const uint8_t *tile_active, int32_t tiles_x) {
         t0(T_FILM); hipLaunchKernelGGL(k_export_samples_tiles, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, P, out, tile_active, tiles_x); t1();
     }
+    // ---- the tile form of an AOV pass (render_aov_impl with tile flags): film_aov and export_aov for the active tiles
+    void film_aov_tiles(uint32_t planes, const DAovFilm &films, int32_t y0, int32_t y1, const DParams &Rf, const uint32_t *tile_list, uint32_t n_list, int32_t tiles_x) {
+        const DAov A = aov_arrays(aov_depth_plane(planes));
+        DPaths Pf = P;
+        if (A.pfilm) Pf.pfilm = A.pfilm;
+        if (n_lanes > 1 && film_prev) (void)hipStreamWaitEvent(stream, film_prev, 0); // pass order, whichever lane (film())
+        if (opt.aov_fused_film) {
+            DAovFilm F = films;
+            for (uint32_t k = 0; k < AOV_PLANES; ++k) if (!(planes & (1u << k))) F.plane[k] = nullptr;
+            t0(T_FILM); hipLaunchKernelGGL(k_film_aov_tiles, dim3(n_list), dim3(BLOCK), 0, stream, Rf, S, Pf, A, (const float *)ps->table.p, F, y0, y1, tiles_x, tile_list); t1();
+        } else {
+            v4 *const src[AOV_PLANES] = {A.albedo, A.normal, A.depthp};
+            for (uint32_t k = 0; k < AOV_PLANES; ++k) {
+                if (!(planes & (1u << k))) continue;
+                DPaths Pk = Pf; Pk.L = src[k]; // the beauty's tile gather with the plane as its radiance
+                t0(T_FILM); hipLaunchKernelGGL(k_film_tiles, dim3(n_list), dim3(BLOCK), 0, stream, Rf, S, Pk, (const float *)ps->table.p, films.plane[k], y0, y1, tiles_x, tile_list); t1();
+            }
+        }
+        if (n_lanes > 1) { film_prev = ps->lane_ev[cur]; (void)hipEventRecord(film_prev, stream); }
+    }
+    void export_aov_tiles(float *out, uint32_t off, const uint8_t *tile_active, int32_t tiles_x) {
+        t0(T_FILM); hipLaunchKernelGGL(k_export_aov_tiles, dim3(grid_for(R.n_paths)), dim3(BLOCK), 0, stream, R, S, aov_arrays(false), off, out, tile_active, tiles_x); t1();
+    }
     void end(PtrsStats &st) {
         for (uint32_t l = 0; l < n_lanes; ++l) { select(l); if (hipStreamSynchronize(stream) != hipSuccess) rc = PTRS_ERR_DEVICE; }
         select(0);
@@ -2108,8 +2131,9 @@ int aov_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderP
     return require_device();
 }
 
-int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, uint32_t planes, const DAovFilm &films, float *samples_dev, hipStream_t stream, PtrsStats *stats) {
-    return with_backend(ps, prm, stream, [&](HipBackend &be, std::string &err) { return render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err); });
+int do_render_aov(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm, uint32_t planes, const DAovFilm &films, float *samples_dev, hipStream_t stream, PtrsStats *stats,
+                  const RenderJob &job = RenderJob{} /* its sample range and tile fields */) {
+    return with_backend(ps, prm, stream, [&](HipBackend &be, std::string &err) { return render_aov_impl(be, ps->sc, ps->H, ps->H.max_depth, *cam, *prm, planes, films, samples_dev, stats, err, job); });
 }
 
 // The error of a device film against its half film: tile records into tiles_dev, the summary through sum_dev into host memory; on
@@ -2160,6 +2184,110 @@ int upload_tiles(PtrsScene *ps, const PtrsRenderParams &prm, const uint8_t *flag
     HIPCHK(hipMemcpy(ps->ad_flags.p, flags01.data(), n_tiles, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ps->ad_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
     job.tile_active = (const uint8_t *)ps->ad_flags.p; job.tile_active_host = flags01.data(); job.tile_list = (const uint32_t *)ps->ad_list.p; job.n_tile_list = n_active;
+    return PTRS_OK;
+}
+
+// ptrs_render_aov_range / ptrs_render_aov_tiles and their device forms: ptrs_render_aov's checks, then ptrs_render_range's (the tile
+// form: ptrs_render_tiles') with their messages, then that there is a device
+int aov_range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes, const void *const *plane_ptrs,
+                         bool tile_form, RowBand *band_out) {
+    if (!scene || !camera || !params) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
+    for (uint32_t k = 0; k < AOV_PLANES; ++k)
+        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
+    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
+    if (tile_form && params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+    RowBand band;
+    int rc = row_band(*params, band);
+    if (rc != PTRS_OK) return rc;
+    if (band_out) *band_out = band;
+    return require_device();
+}
+DAovFilm device_planes(uint32_t planes, void *const *ptrs) {
+    DAovFilm F;
+    for (uint32_t k = 0; k < AOV_PLANES; ++k) F.plane[k] = (planes & (1u << k)) ? (v4 *)ptrs[k] : nullptr;
+    return F;
+}
+// The host form of the calls above: the band of every plane asked for travels to the scene's device copies, run(films, samples) does
+// the device's part, the band travels back.  The sample export starts from the caller's buffer: the entries the call does not write
+// (outside the range, inactive sample pixels) keep what they held.
+template <class Run> int aov_host_planes(PtrsScene *scene, const PtrsRenderParams *params, const RowBand &band, uint32_t planes, PtrsFilmPixel *const *planes_inout, float *sample_aov, Run run) {
+    HIPCHK(hipSetDevice(scene->device));
+    int rc;
+    DAovFilm F;
+    for (uint32_t k = 0; k < AOV_PLANES; ++k) {
+        F.plane[k] = nullptr;
+        if (!(planes & (1u << k))) continue;
+        if ((rc = stage_in(scene->aov_film_tmp[k], *params, band, planes_inout[k])) != PTRS_OK) return rc;
+        F.plane[k] = (v4 *)scene->aov_film_tmp[k].p;
+    }
+    const size_t sbytes = sample_aov ? sample_buffer_bytes(*params, PTRS_AOV_SAMPLE_FLOATS) : 0;
+    if (sample_aov) {
+        if ((rc = scene->aov_samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
+        HIPCHK(hipMemcpy(scene->aov_samples_tmp.p, sample_aov, sbytes, hipMemcpyHostToDevice));
+    }
+    if ((rc = run(F, sample_aov ? (float *)scene->aov_samples_tmp.p : nullptr)) != PTRS_OK) return rc;
+    for (uint32_t k = 0; k < AOV_PLANES; ++k)
+        if (F.plane[k] && (rc = stage_out(scene->aov_film_tmp[k], band, planes_inout[k])) != PTRS_OK) return rc;
+    if (sample_aov) HIPCHK(hipMemcpy(sample_aov, scene->aov_samples_tmp.p, sbytes, hipMemcpyDeviceToHost));
+    return PTRS_OK;
+}
+
+// ptrs_render_aov_adaptive: the planes of a film whose tile t holds tile_spp[t] samples of the schedule.  Block k = [begin_k, end_k) runs
+// on the tiles with tile_spp[t] >= end_k; consecutive blocks with the same tile set are one run, a block without a tile is none.
+struct AovRun { uint32_t begin, end; std::vector<uint8_t> tiles; };
+int aov_adaptive_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes, const void *const *plane_ptrs,
+                            std::vector<AovRun> &runs, RowBand *band_out) {
+    if (!scene || !camera || !params || !tile_spp) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
+    for (uint32_t k = 0; k < AOV_PLANES; ++k)
+        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
+    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
+    uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
+    if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
+    const uint32_t n_tiles = (uint32_t)ad_tiles_x(params->width) * (uint32_t)ad_tiles_y(params->height);
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        bool ok = tile_spp[t] == 0u;
+        for (uint32_t k = 0; k < n_blocks && !ok; ++k) ok = tile_spp[t] == blocks[3 * k + 2];
+        if (!ok) { g_err = "render_aov_adaptive: tile_spp[" + std::to_string(t) + "] = " + std::to_string(tile_spp[t]) + " is neither 0 nor the end of a block of the schedule"; return PTRS_ERR_INVALID; }
+    }
+    runs.clear();
+    for (uint32_t k = 0; k < n_blocks; ++k) {
+        std::vector<uint8_t> set(n_tiles);
+        bool any = false;
+        for (uint32_t t = 0; t < n_tiles; ++t) { set[t] = tile_spp[t] >= blocks[3 * k + 2] ? 1 : 0; any = any || set[t]; }
+        if (!any) continue;
+        if (!runs.empty() && runs.back().end == blocks[3 * k] && runs.back().tiles == set) runs.back().end = blocks[3 * k + 2];
+        else runs.push_back(AovRun{blocks[3 * k], blocks[3 * k + 2], std::move(set)});
+    }
+    RowBand band;
+    PtrsRenderParams whole = *params; whole.row_begin = 0; whole.row_end = 0;
+    int rc = row_band(whole, band);
+    if (rc != PTRS_OK) return rc;
+    if (band_out) *band_out = band;
+    return require_device();
+}
+int do_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, const std::vector<AovRun> &runs, uint32_t planes, const DAovFilm &F, hipStream_t stream, PtrsStats *stats) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(scene->device));
+    PtrsStats total; std::memset(&total, 0, sizeof(total));
+    for (const AovRun &run : runs) {
+        const uint32_t range[2] = {run.begin, run.end};
+        HipJob job;
+        job.sample_range = range;
+        std::vector<uint8_t> flags01; uint32_t n_active = 0;
+        int rc = upload_tiles(scene, *params, run.tiles.data(), flags01, job, n_active);
+        if (rc != PTRS_OK) return rc;
+        PtrsStats st;
+        if ((rc = do_render_aov(scene, camera, params, planes, F, nullptr, stream, &st, job)) != PTRS_OK) return rc;
+        total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
+        total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
+        total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
+    }
+    total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = total;
     return PTRS_OK;
 }
 
@@ -2685,6 +2813,89 @@ int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsR
         total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         if (stats) *stats = total;
         return PTRS_OK;
+    });
+}
+
+// ---- feature planes for sample ranges and tiles; the planes of an adaptive film ------------------------------------------
+int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
+                                 void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout_device, false, nullptr);
+        if (rc != PTRS_OK) return rc;
+        const uint32_t range[2] = {sample_begin, sample_end};
+        RenderJob job;
+        job.sample_range = range;
+        return do_render_aov(scene, camera, params, planes, device_planes(planes, planes_inout_device), sample_aov_device, (hipStream_t)hip_stream, stats, job);
+    });
+}
+
+int ptrs_render_aov_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
+                          PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        RowBand band;
+        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout, false, &band);
+        if (rc != PTRS_OK) return rc;
+        const uint32_t range[2] = {sample_begin, sample_end};
+        RenderJob job;
+        job.sample_range = range;
+        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
+    });
+}
+
+int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
+                                 uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        if (!tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout_device, true, nullptr);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipSetDevice(scene->device));
+        const uint32_t range[2] = {sample_begin, sample_end};
+        HipJob job;
+        job.sample_range = range;
+        std::vector<uint8_t> flags01; uint32_t n_active = 0;
+        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
+        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; } // no tile is active: no launch, the planes stay
+        return do_render_aov(scene, camera, params, planes, device_planes(planes, planes_inout_device), sample_aov_device, (hipStream_t)hip_stream, stats, job);
+    });
+}
+
+int ptrs_render_aov_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
+                          uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        if (!tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        RowBand band;
+        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout, true, &band);
+        if (rc != PTRS_OK) return rc;
+        HIPCHK(hipSetDevice(scene->device));
+        const uint32_t range[2] = {sample_begin, sample_end};
+        HipJob job;
+        job.sample_range = range;
+        std::vector<uint8_t> flags01; uint32_t n_active = 0;
+        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
+        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
+        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
+    });
+}
+
+int ptrs_render_aov_adaptive_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
+                                    void *const planes_inout_device[PTRS_AOV_PLANES], void *hip_stream, PtrsStats *stats) {
+    return guarded([&]() -> int {
+        std::vector<AovRun> runs;
+        int rc = aov_adaptive_check_args(scene, camera, params, min_spp, tile_spp, planes, (const void *const *)planes_inout_device, runs, nullptr);
+        if (rc != PTRS_OK) return rc;
+        return do_render_aov_adaptive(scene, camera, params, runs, planes, device_planes(planes, planes_inout_device), (hipStream_t)hip_stream, stats);
+    });
+}
+
+int ptrs_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
+                             PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], PtrsStats *stats) {
+    return guarded([&]() -> int {
+        std::vector<AovRun> runs;
+        RowBand band;
+        int rc = aov_adaptive_check_args(scene, camera, params, min_spp, tile_spp, planes, (const void *const *)planes_inout, runs, &band);
+        if (rc != PTRS_OK) return rc;
+        // (the planes travel once: the blocks run on the device copies)
+        return aov_host_planes(scene, params, band, planes, planes_inout, nullptr, [&](const DAovFilm &F, float *) { return do_render_aov_adaptive(scene, camera, params, runs, planes, F, nullptr, stats); });
     });
 }
 

@@ -51,7 +51,8 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;                     // next to render.png: denoised.png (ptrs_denoise on the film and the first-hit planes, default parameters)
         else if (a == "--target_error") target_error = std::atof(need("--target_error"));  // render blocks of samples (--min_samples, then doubling, at most -s) until ptrs_film_error's
         else if (a == "--min_samples") min_samples = std::atoi(need("--min_samples"));     // largest tile error is below E (ptrs_render_converged); prints every check and the count it stopped at
-        else if (a == "--adaptive") adaptive = true;                   // with --target_error: every block only on the 16 x 16 tiles still above E (ptrs_render_adaptive); writes samples.png next to render.png
+        else if (a == "--adaptive") adaptive = true;                   // with --target_error: every block only on the 16 x 16 tiles still above E (ptrs_render_adaptive); writes samples.png next to render.png;
+                                                                       // --aov / --denoise then take their planes from ptrs_render_aov_adaptive: every tile's planes hold the samples its film pixels hold
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
@@ -76,6 +77,8 @@ int main(int argc, char **argv) {
         if (done < total && !write_png_rgba8(out_dir + "/render.png", camera.film.width, camera.film.height, camera.film.to_rgba_image(), e)) std::fprintf(stderr, "\nwarning: preview: %s\n", e.c_str());
     };
     PtrsStats st{};
+    std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES];
+    bool have_planes = false; // --adaptive: the planes are rendered tile by tile with the samples the film's tiles hold
     auto t0 = std::chrono::steady_clock::now();
     int rc;
     if (n_gpus > 1) {
@@ -106,6 +109,12 @@ int main(int argc, char **argv) {
                 }
             if (!write_png_rgba8(out_dir + "/samples.png", camera.film.width, camera.film.height, img, err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
             std::fprintf(stderr, "INFO wrote %s/samples.png\n", out_dir.c_str());
+            if (aov || denoise) { // (before the sample count changes: the schedule's ceiling is -s)
+                PtrsStats ast{};
+                rc = integrator.render_aov_adaptive(camera, scene, (uint32_t)(min_samples < 0 ? 0 : min_samples), tile_spp, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, &ast);
+                if (rc != PTRS_OK) { std::fprintf(stderr, "error: aov render failed (%d): %s\n", rc, integrator.last_error.c_str()); return 1; }
+                have_planes = true;
+            }
             integrator.set_samples_per_pixel((int)res.spp_done);
         }
     } else if (target_error >= 0.0) {
@@ -124,9 +133,8 @@ int main(int argc, char **argv) {
     const std::string out = out_dir + "/render.png"; // main.rs:70
     if (!write_png_rgba8(out, camera.film.width, camera.film.height, camera.film.to_rgba_image(), err)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
     std::fprintf(stderr, "INFO wrote %s\n", out.c_str());
-    std::vector<PtrsFilmPixel> planes[PTRS_AOV_PLANES];
     if (aov) {
-        rc = integrator.render_aov(camera, scene, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, &st);
+        rc = have_planes ? PTRS_OK : integrator.render_aov(camera, scene, PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH, planes, &st);
         if (rc != PTRS_OK) { std::fprintf(stderr, "error: aov render failed (%d): %s\n", rc, integrator.last_error.c_str()); return 1; }
         std::vector<uint8_t> img[PTRS_AOV_PLANES];
         aov_to_rgba_images(camera.film.width, camera.film.height, planes, img);

@@ -210,6 +210,22 @@ int PathIntegrator::render_adaptive(Camera &camera, RenderScene &scene, float ta
     if (rc != PTRS_OK) last_error = ptrs_last_error();
     return rc;
 }
+int PathIntegrator::render_aov_adaptive(Camera &camera, RenderScene &scene, uint32_t min_spp, const std::vector<uint32_t> &tile_spp, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    const PtrsRenderParams p = params(camera);
+    const size_t npx = (size_t)camera.film.width * (size_t)camera.film.height;
+    if (tile_spp.size() != (size_t)((p.width + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE) * (size_t)((p.height + PTRS_ERROR_TILE - 1) / PTRS_ERROR_TILE)) { last_error = "render_aov_adaptive: tile_spp must have tiles_x * tiles_y entries"; return PTRS_ERR_INVALID; }
+    PtrsFilmPixel *ptrs[PTRS_AOV_PLANES] = {nullptr, nullptr, nullptr};
+    for (uint32_t k = 0; k < PTRS_AOV_PLANES; ++k) {
+        if (!(planes & (1u << k))) continue;
+        if (planes_inout[k].size() != npx) planes_inout[k].assign(npx, PtrsFilmPixel{{0, 0, 0}, 0});
+        ptrs[k] = planes_inout[k].data();
+    }
+    rc = ptrs_render_aov_adaptive(gpu_scene_, &camera.abi, &p, min_spp, tile_spp.data(), planes, ptrs, stats);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
 int PathIntegrator::render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats) {
     int rc = ensure_scene(scene);
     if (rc != PTRS_OK) return rc;

@@ -106,6 +106,9 @@ public:
     // ptrs_render_adaptive: the same schedule, every block on the 16 x 16 tiles whose error has not been below target_error yet.
     // tile_spp (may be null): tiles_x * tiles_y entries, the samples each tile's pixels hold.
     int render_adaptive(Camera &camera, RenderScene &scene, float target_error, uint32_t min_spp, PtrsAdaptiveResult &result, std::vector<uint32_t> *tile_spp = nullptr, PtrsStats *stats = nullptr);
+    // ptrs_render_aov_adaptive: the planes of the film render_adaptive left -- tile t of every plane holds tile_spp[t] samples of the
+    // same schedule (the sampler's spp is still the ceiling).  Planes are accumulated into like render_aov's.
+    int render_aov_adaptive(Camera &camera, RenderScene &scene, uint32_t min_spp, const std::vector<uint32_t> &tile_spp, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats = nullptr);
     // ptrs_render_tiles: samples [sample_begin, sample_end) on the active tiles (tiles_x * tiles_y flag bytes) into camera.film
     int render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats = nullptr);
     // another sample count for the renders that follow (the planes of render_aov at the count render_converged stopped at)

@@ -59,6 +59,13 @@ def load_library():
     L.ptrs_render_tiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptrs_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptrs_adaptive_freeze.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.ptrs_render_aov_range.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.ptrs_render_aov_range_device.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.ptrs_render_aov_tiles.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp, vp]
+    L.ptrs_render_aov_tiles_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.ptrs_render_aov_adaptive.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp]
+    L.ptrs_render_aov_adaptive_device.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
     L.ptrs_set_option.argtypes = [C.c_char_p, C.c_int64]
     L.ptrs_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.ptrs_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
@@ -394,9 +401,147 @@ class PathIntegrator:
             out["half"] = half
         return out
 
-    def render_denoised(self, camera, scene, **params):
+    def _aov_host_planes(self, p, planes, into, what):
+        """The planes asked for as host arrays (those given in `into`, else zeros) and the pointer array of the ptrs_render_aov_* calls."""
+        mask, out = _aov_mask(planes), {}
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)()
+        for k, name in enumerate(abi.PtrsAovNames):
+            if mask & (1 << k):
+                a = into.get(name) if into else None
+                if a is None:
+                    a = np.zeros((p.height, p.width), dtype=abi.FILM_DTYPE)
+                if a.dtype != abi.FILM_DTYPE or a.shape != (p.height, p.width) or not a.flags.c_contiguous:
+                    raise PtrsError("%s: plane %s must be a contiguous (H, W) FILM_DTYPE array" % (what, name))
+                out[name] = a
+                ptrs[k] = a.ctypes.data
+        return mask, out, ptrs
+
+    @staticmethod
+    def _aov_device_planes(planes, plane_device_ptrs):
+        mask = _aov_mask(planes)
+        ptrs = (C.c_void_p * abi.PtrsAovPlanes)()
+        for k, name in enumerate(abi.PtrsAovNames):
+            if mask & (1 << k) and plane_device_ptrs.get(name):
+                ptrs[k] = int(plane_device_ptrs[name])
+        return mask, ptrs
+
+    def _aov_samples_arg(self, p, samples, what):
+        if samples is None:
+            return None
+        spp = p.spp if p.sampler == abi.SAMPLER_STRATIFIED else round_up_pow2(p.spp)
+        if samples.dtype != np.float32 or samples.shape != (p.height + 4, p.width + 4, spp, abi.PtrsAovSampleFloats) or not samples.flags.c_contiguous:
+            raise PtrsError("%s: samples must be a contiguous (H + 4, W + 4, spp, 12) float32 array" % what)
+        return samples.ctypes.data
+
+    def render_aov_range(self, camera, scene, sample_begin, sample_end, planes=("albedo", "normal", "depth"), row_begin=0, row_end=0, samples=None, into=None):
+        """ptrs_render_aov_range: samples [sample_begin, sample_end) of render_aov's call (the sampler's spp stays the whole render's
+        count), accumulated into the planes of `into` (absent ones start from zero).  samples: None, or the (H + 4, W + 4, spp, 12)
+        array of render_aov(want_samples=True), of which only the range's entries are written.  Ranges that tile [0, spp) in order give
+        render_aov's planes and samples bit for bit under every pass plan.  Returns the dict of planes."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, out, ptrs = self._aov_host_planes(p, planes, into, "render_aov_range")
+        _check(load_library().ptrs_render_aov_range(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), mask, ptrs,
+                                                    self._aov_samples_arg(p, samples, "render_aov_range"), C.addressof(stats)))
+        self.last_stats = stats
+        return out
+
+    def render_aov_range_device(self, camera, scene, sample_begin, sample_end, plane_device_ptrs, planes=("albedo", "normal", "depth"), stream=0, row_begin=0, row_end=0,
+                                samples_device_ptr=0):
+        """Same, the planes (and the sample export, 0: none) in device memory."""
+        ds = _device_scene(scene, self.device)
+        p = self.params(camera, row_begin, row_end)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, ptrs = self._aov_device_planes(planes, plane_device_ptrs)
+        _check(load_library().ptrs_render_aov_range_device(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), mask, ptrs,
+                                                           int(samples_device_ptr) or None, int(stream) or None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_aov_tiles(self, camera, scene, sample_begin, sample_end, tiles, planes=("albedo", "normal", "depth"), samples=None, into=None):
+        """ptrs_render_aov_tiles: render_aov_range restricted to the active tiles (`tiles` as in render_tiles, the same dilation rule).
+        The pixels of the active tiles end with render_aov_range's bits in every plane asked for, all others keep theirs; of `samples`
+        only the range's entries of the active sample pixels are written.  Returns the dict of planes."""
+        p = self.params(camera, 0, 0)
+        tf = self._tile_flags(p, tiles, "render_aov_tiles")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, out, ptrs = self._aov_host_planes(p, planes, into, "render_aov_tiles")
+        _check(load_library().ptrs_render_aov_tiles(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), tf.ctypes.data, mask, ptrs,
+                                                    self._aov_samples_arg(p, samples, "render_aov_tiles"), C.addressof(stats)))
+        self.last_stats = stats
+        return out
+
+    def render_aov_tiles_device(self, camera, scene, sample_begin, sample_end, tiles, plane_device_ptrs, planes=("albedo", "normal", "depth"), stream=0, samples_device_ptr=0):
+        """Same, the planes (and the sample export, 0: none) in device memory; `tiles` stays a host array."""
+        p = self.params(camera, 0, 0)
+        tf = self._tile_flags(p, tiles, "render_aov_tiles_device")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, ptrs = self._aov_device_planes(planes, plane_device_ptrs)
+        _check(load_library().ptrs_render_aov_tiles_device(ds.handle, C.addressof(cam), C.addressof(p), int(sample_begin), int(sample_end), tf.ctypes.data, mask, ptrs,
+                                                           int(samples_device_ptr) or None, int(stream) or None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def _tile_spp_arg(self, p, tile_spp, what):
+        T = abi.PtrsErrorTile
+        shape = ((p.height + T - 1) // T, (p.width + T - 1) // T)
+        ts = np.ascontiguousarray(tile_spp, dtype=np.uint32)
+        if ts.size != shape[0] * shape[1]:
+            raise PtrsError("%s: tile_spp must have tiles_y x tiles_x = %d x %d entries" % (what, shape[0], shape[1]))
+        return ts
+
+    def render_aov_adaptive(self, camera, scene, tile_spp, min_spp=8, planes=("albedo", "normal", "depth"), into=None):
+        """ptrs_render_aov_adaptive: the planes of a film whose tile t holds tile_spp[t] samples of converge_schedule(spp, min_spp) --
+        render_adaptive's tile_spp.  Tile t of every plane is tile t of render_aov_range(0, tile_spp[t]); a tile with 0 keeps its bits;
+        from cleared planes the weights equal those of the render_adaptive film that produced tile_spp.  Returns the dict of planes."""
+        p = self.params(camera, 0, 0)
+        ts = self._tile_spp_arg(p, tile_spp, "render_aov_adaptive")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, out, ptrs = self._aov_host_planes(p, planes, into, "render_aov_adaptive")
+        _check(load_library().ptrs_render_aov_adaptive(ds.handle, C.addressof(cam), C.addressof(p), int(min_spp), ts.ctypes.data, mask, ptrs, C.addressof(stats)))
+        self.last_stats = stats
+        return out
+
+    def render_aov_adaptive_device(self, camera, scene, tile_spp, plane_device_ptrs, min_spp=8, planes=("albedo", "normal", "depth"), stream=0):
+        """Same, the planes in device memory; tile_spp stays a host array."""
+        p = self.params(camera, 0, 0)
+        ts = self._tile_spp_arg(p, tile_spp, "render_aov_adaptive_device")
+        ds = _device_scene(scene, self.device)
+        cam = camera.to_abi()
+        stats = abi.PtrsStats()
+        mask, ptrs = self._aov_device_planes(planes, plane_device_ptrs)
+        _check(load_library().ptrs_render_aov_adaptive_device(ds.handle, C.addressof(cam), C.addressof(p), int(min_spp), ts.ctypes.data, mask, ptrs, int(stream) or None, C.addressof(stats)))
+        self.last_stats = stats
+        return stats
+
+    def render_denoised(self, camera, scene, target_error=None, min_spp=8, adaptive=False, **params):
         """render, then render_aov, then Denoiser.denoise (params: iterations, sigma_color, sigma_normal, sigma_depth, demodulate).  The
-        noisy film stays in camera.film; returns the denoised (H, W) FILM_DTYPE pixels (rgb = colour, weight = 1)."""
+        noisy film stays in camera.film; returns the denoised (H, W) FILM_DTYPE pixels (rgb = colour, weight = 1).  With target_error:
+        render_converged (adaptive: render_adaptive) in place of render, and planes that hold exactly the film's samples --
+        render_aov_range(0, spp_done), or render_aov_adaptive on the tile_spp the render returned; the render's result is kept in
+        self.last_converge."""
+        if target_error is not None:
+            if adaptive:
+                res = self.render_adaptive(camera, scene, target_error, min_spp)
+                planes = self.render_aov_adaptive(camera, scene, res["tile_spp"], min_spp)
+            else:
+                res = self.render_converged(camera, scene, target_error, min_spp)
+                planes = self.render_aov_range(camera, scene, 0, res["spp_done"])
+            self.last_converge = res
+            dn = Denoiser(camera.film.width, camera.film.height, self.device)
+            try:
+                return dn.denoise(camera.film.pixels, planes, **params)
+            finally:
+                dn.close()
         self.render(camera, scene)
         planes = self.render_aov(camera, scene)
         dn = Denoiser(camera.film.width, camera.film.height, self.device)
