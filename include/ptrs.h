@@ -590,6 +590,25 @@ int ptrs_probe_surface(PtrsScene *scene, int32_t prim, uint32_t n, const float *
  *   20 p, p_error, n, w (in0..11): offset_ray_origin, spawn_pair plus, minus, spawn_from
  *   21 u = in0, size = bits(in1) in 2..14, cdf = in2..: find_interval_cdf, find_interval_cdf_guided (guide table built from the cdf) */
 int ptrs_probe_math(int32_t device, uint32_t op, uint32_t n, const float *rows, float *out);
+/* ptrs_probe_shade_tables (device only): the shade kernels' workgroup tables -- the round's Sobol' window in nibble form, the triangle and
+ * light records, the environment light's marginal tables -- staged into LDS arrays of the shade kernels' sizes exactly as round `it` of
+ * a render of `scene` with `params` stages them (the sampler, the feature set and the staging configuration come from the render
+ * path's own code; nothing is rendered), then one row per thread through that context.  Rows are 12 32-bit words in, 12 out.
+ * header_out receives 12 words: sob_lo, sob_n (the window is dimensions [sob_lo, sob_lo + sob_n)), sob_nib (index nibbles staged per
+ * dimension: 8 or 13), tri_lds (1: the triangle records are staged), n_lights_lds (light records staged), marg_li (the environment light
+ * whose marginal tables the shade kernels stage, 0xffffffff: none), pre_li (the environment light whose samples are computed ahead of the
+ * shade kernels, 0xffffffff: none), the shade kernels' feature set (csrc/pt_texture.h FEAT_*), 1 when the render runs the shade kernels
+ * built without the in-kernel environment walk, 0, 0, 0.
+ *   op 0, Sobol' draws: row = index low word, index high word, scramble, N (1, 2, 3 or 8), N dimensions (each < 1024), rest unused;
+ *         out = the N values of the shade context's batched draw as binary32 bit patterns in words 0..N-1, word 8 = the route taken:
+ *         0 the global tables, 1 the 8-nibble run of consecutive dimensions, 2 the general loop over the staged nibbles.
+ *   op 1, environment sample: row = u.x, u.y (binary32 in [0, 1)), light index (an environment light of the scene); out = the light's
+ *         sample for u with the light record and the marginal tables taken from where the shade kernels take them: wi.xyz, pdf, Li.rgb
+ *         (binary32), ok (0 / 1), then 1 when the marginal tables came from LDS.
+ * NULL buffers, n == 0, more than PTRS_PROBE_MAX_ROWS rows, an unknown op, an N other than 1, 2, 3, 8, a dimension >= 1024, a u outside
+ * [0, 1) and a round `it` above 65535 are refused before a device is touched. */
+int ptrs_probe_shade_tables(PtrsScene *scene, const PtrsRenderParams *params, uint32_t it, uint32_t op, uint32_t n, const uint32_t *rows,
+                            uint32_t *out, uint32_t *header_out);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,14 @@ PtrsAovNames = ("albedo", "normal", "depth")
  MATH_ROUND, MATH_MINMAX, MATH_MINMAX_NZ, MATH_U2F, MATH_INT, MATH_NEXT, MATH_SOLVE, MATH_FRAME, MATH_SPAWN, MATH_SEARCH, MATH_NUM_OPS) = range(23)
 PROBE_MATH_WIDTH = 16
 PROBE_MATH_ARGTYPES = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+# ptrs_probe_shade_tables: ops, 32-bit words per row (in and out) and of the header, the header's fields in order, the Sobol' routes
+PROBE_SHADE_SOBOL, PROBE_SHADE_ENV, PROBE_SHADE_NUM_OPS = range(3)
+PROBE_SHADE_WIDTH = 12
+PROBE_SHADE_HEADER = ("sob_lo", "sob_n", "sob_nib", "tri_lds", "n_lights_lds", "marg_li", "pre_li", "feat", "envpre")
+PROBE_SHADE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+SOB_ROUTE_GLOBAL, SOB_ROUTE_RUN, SOB_ROUTE_LOOP = range(3)
+FEAT_SIMPLE, FEAT_IMG, FEAT_IMG_ENV, FEAT_FULL = 0, 1, 3, 15  # the shade kernels' feature sets (csrc/pt_texture.h)
+NO_LIGHT = 0xffffffff
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)

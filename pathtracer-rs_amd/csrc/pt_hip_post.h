@@ -383,3 +383,47 @@ __global__ __launch_bounds__(BLOCK) void k_probe_math(uint32_t op, uint32_t n, c
     if (i >= n) return;
     math_probe_row(op, in + (uint64_t)i * PROBE_MATH_IN, out + (uint64_t)i * PROBE_MATH_OUT);
 }
+
+// The shade stage's LDS context at rows of the test's choosing (ptrs_probe_shade_tables): the tables staged by stage_shade_tables into
+// arrays of the shade kernels' sizes, the barrier, then one row per thread through ShadeCtxLds.  MARG: the instantiations that stage the
+// environment light's marginal tables (scenes with FEAT_INFINITE); the staging code does not depend on the feature set otherwise.
+template <int N>
+__device__ inline void probe_shade_sobol_row(const ShadeCtxLds<false> &X, const DSampler &S, const uint32_t *in, uint32_t *out) {
+    const uint64_t index = (uint64_t)in[0] | ((uint64_t)in[1] << 32);
+    uint32_t dim[N], route = 0xffffffffu;
+    float v[N];
+    for (int k = 0; k < N; ++k) dim[k] = in[4 + k];
+    X.template sobol<N, true>(S, index, dim, in[2], v, &route);
+    for (int k = 0; k < N; ++k) out[k] = f2u(v[k]);
+    out[8] = route;
+}
+template <bool MARG>
+__global__ __launch_bounds__(BLOCK) void k_probe_shade(DSampler S, DScene sc, ShadeLdsCfg cfg, uint32_t op, uint32_t n, const uint32_t *__restrict__ in, uint32_t *__restrict__ out) {
+    __shared__ uint32_t lds_sob[SH_SOB_WORDS];
+    __shared__ v4 lds_tri[SH_TRI_V4];
+    __shared__ v4 lds_light[SH_LIGHTS * SH_LIGHT_V4];
+    __shared__ float lds_marg[MARG ? SH_MARG_WORDS : 1];
+    const ShadeCtxLds<false> X = stage_shade_tables<MARG ? FEAT_IMG_ENV : FEAT_SIMPLE, false>(S, sc, cfg, lds_sob, lds_tri, lds_light, lds_marg);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *r = in + (uint64_t)i * PROBE_SHADE_IN;
+    uint32_t *o = out + (uint64_t)i * PROBE_SHADE_OUT;
+    for (uint32_t k = 0; k < PROBE_SHADE_OUT; ++k) o[k] = 0u;
+    if (op == PROBE_SHADE_SOBOL) {
+        switch (r[3]) { // (the entry point has checked N)
+            case 1: probe_shade_sobol_row<1>(X, S, r, o); break;
+            case 2: probe_shade_sobol_row<2>(X, S, r, o); break;
+            case 3: probe_shade_sobol_row<3>(X, S, r, o); break;
+            default: probe_shade_sobol_row<8>(X, S, r, o); break;
+        }
+    } else { // PROBE_SHADE_ENV: the light's record and its marginal tables from where shade_item takes them
+        const uint32_t li = r[2];
+        DLight Lt;
+        X.light(sc, li, Lt);
+        f3 wi, rgb; float pdf;
+        const bool ok = inf_light_sample(sc, Lt, mk2(u2f(r[0]), u2f(r[1])), wi, pdf, rgb, X.inf_marginal(li));
+        o[0] = f2u(wi.x); o[1] = f2u(wi.y); o[2] = f2u(wi.z); o[3] = f2u(pdf); o[4] = f2u(rgb.x); o[5] = f2u(rgb.y); o[6] = f2u(rgb.z); o[7] = ok ? 1u : 0u;
+        o[8] = X.inf_marginal(li) ? 1u : 0u;
+    }
+}

@@ -14,7 +14,28 @@
 namespace pt {
 
 enum : uint32_t { PROBE_BSDF_IN = 8, PROBE_BSDF_OUT = 16, PROBE_LIGHT_IN = 5, PROBE_LIGHT_OUT = 16, PROBE_TEX_IN = 6, PROBE_TEX_OUT = 8,
-                  PROBE_SURF_IN = 16, PROBE_SURF_OUT = 64, PROBE_MATH_IN = 16, PROBE_MATH_OUT = 16 };
+                  PROBE_SURF_IN = 16, PROBE_SURF_OUT = 64, PROBE_MATH_IN = 16, PROBE_MATH_OUT = 16,
+                  PROBE_SHADE_IN = 12, PROBE_SHADE_OUT = 12, PROBE_SHADE_HEADER = 12 /* 32-bit words: ptrs_probe_shade_tables (device only) */ };
+enum : uint32_t { PROBE_SHADE_SOBOL = 0, PROBE_SHADE_ENV = 1, PROBE_SHADE_NUM_OPS };
+
+// ptrs_probe_shade_tables' checks of its rows (no device needed): nullptr, or why the call is refused.  A Sobol' row draws N of 1, 2, 3
+// or 8 dimensions below 1024 (the batch sizes shade_item draws; the tables end at 1024); an environment row samples an
+// InfiniteAreaLight of the scene with u in [0, 1)^2.  H == nullptr: the checks that need no scene.
+inline const char *probe_shade_rows_check(const HostScene *H, uint32_t op, uint32_t n, const uint32_t *rows) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t *r = rows + (size_t)i * PROBE_SHADE_IN;
+        if (op == PROBE_SHADE_SOBOL) {
+            const uint32_t N = r[3];
+            if (N != 1u && N != 2u && N != 3u && N != 8u) return "a Sobol' row draws 1, 2, 3 or 8 dimensions";
+            for (uint32_t k = 0; k < N; ++k) if (r[4 + k] >= 1024u) return "sobol sampler can only sample up to 1024 dimensions";
+        } else {
+            float u[2]; std::memcpy(u, r, 8);
+            if (!(u[0] >= 0.0f && u[0] < 1.0f && u[1] >= 0.0f && u[1] < 1.0f)) return "u outside [0, 1)";
+            if (H && ((size_t)r[2] >= H->lights.size() || H->lights[r[2]].kind != 3)) return "the row's light is not an environment light of the scene";
+        }
+    }
+    return nullptr;
+}
 
 // A synthetic hit for a BSDF probe: geometric normal ng, shading normal ns, shading dpdu (the
 // bsdf's ss = normalize(dpdu), ts = ns x ss: the caller passes dpdu orthogonal to ns).

@@ -829,6 +829,7 @@ struct ShadeLdsCfg { uint32_t sob_lo, sob_n, sob_nib, tri_lds, n_lights_lds, mar
 enum : uint32_t { SH_MARG_N = 1024, SH_MARG_WORDS = 3 * SH_MARG_N + 8 }; // row integrals [nv] | their cdf [nv + 1] | the cdf's guide [guide_v + 1], nv and guide_v <= 1024 // Sobol' window [sob_lo, sob_lo + sob_n), nibbles staged per dimension
 typedef __attribute__((address_space(3))) const uint32_t lds_u32;
 PT_HD uint32_t sob_stride(uint32_t nib) { return nib * 16u + 4u; } // words per dimension; + 4: consecutive dimensions start 4 banks apart
+enum : uint32_t { SOB_ROUTE_GLOBAL = 0, SOB_ROUTE_RUN = 1, SOB_ROUTE_LOOP = 2 }; // how ShadeCtxLds::sobol served a batch: the global tables, the 8-nibble run of consecutive dimensions, the general loop over the staged nibbles
 template <bool ENVPRE = false>
 struct ShadeCtxLds {
     static constexpr bool inf_fallback = !ENVPRE; // ENVPRE: the scene's one InfiniteAreaLight is presampled (k_env_presample), shade_item never walks its distribution itself
@@ -852,17 +853,19 @@ struct ShadeCtxLds {
 #pragma unroll
         for (uint32_t k = 0; k < SH_LIGHT_V4; ++k) o[k] = ld(q + k);
     }
-    template <int N> __device__ inline void sobol(const DSampler &S, uint64_t index, const uint32_t (&dim)[N], uint32_t scramble, float (&out)[N]) const {
+    // (ROUTE: ptrs_probe_shade_tables asks which of the three routes a batch took -- SOB_ROUTE_*; the render kernels' instantiations carry none of it)
+    template <int N, bool ROUTE = false> __device__ inline void sobol(const DSampler &S, uint64_t index, const uint32_t (&dim)[N], uint32_t scramble, float (&out)[N], uint32_t *route = nullptr) const {
         const uint32_t lo = (uint32_t)index, hi = (uint32_t)(index >> 32);
         bool in = cfg.sob_nib >= 13u || (hi == 0u && cfg.sob_nib >= 8u); // every set bit of the index has its nibble staged
 #pragma unroll
         for (int k = 0; k < N; ++k) in = in && dim[k] - cfg.sob_lo < cfg.sob_n;
-        if (!in) { sobol_batch<N>(S, index, dim, scramble, out); return; } // outside this round's window: the global tables
+        if (!in) { if constexpr (ROUTE) *route = SOB_ROUTE_GLOBAL; sobol_batch<N>(S, index, dim, scramble, out); return; } // outside this round's window: the global tables
         uint32_t v[N];
         bool run = cfg.sob_nib == 8u; // the common case: N consecutive dimensions, 8 nibbles staged
 #pragma unroll
         for (int k = 1; k < N; ++k) run = run && dim[k] == dim[0] + (uint32_t)k;
         if (run) { // one address per index nibble, the dimension is a compile-time offset of the LDS read
+            if constexpr (ROUTE) *route = SOB_ROUTE_RUN;
             constexpr uint32_t ST = 8u * 16u + 4u; // sob_stride(8)
             lds_u32 *t = sob + (dim[0] - cfg.sob_lo) * ST;
             lds_u32 *t0 = t + (lo & 15u), *t1 = t + 16u + ((lo >> 4) & 15u), *t2 = t + 32u + ((lo >> 8) & 15u), *t3 = t + 48u + ((lo >> 12) & 15u), *t4 = t + 64u + ((lo >> 16) & 15u),
@@ -873,6 +876,7 @@ struct ShadeCtxLds {
             for (int k = 0; k < N; ++k) out[k] = min_nz(PT_ONE_MINUS_EPS, (float)v[k] * 0x1p-32f);
             return;
         }
+        if constexpr (ROUTE) *route = SOB_ROUTE_LOOP;
         const uint32_t stride = sob_stride(cfg.sob_nib);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
@@ -3330,6 +3334,41 @@ int ptrs_probe_math(int32_t device, uint32_t op, uint32_t n, const float *rows, 
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy(out, bo.p, (size_t)n * PROBE_MATH_OUT * 4, hipMemcpyDeviceToHost));
         return PTRS_OK;
+    });
+}
+
+// The shade stage's LDS context as round `it` of a render of `scene` with `params` would build it: render_setup's sampler, the scene's
+// feature set, HipBackend::shade_cfg / presample_li / env_presampled_only -- the render path's own code, nothing restated -- then one
+// launch of k_probe_shade over the rows.
+int ptrs_probe_shade_tables(PtrsScene *scene, const PtrsRenderParams *params, uint32_t it, uint32_t op, uint32_t n, const uint32_t *rows, uint32_t *out, uint32_t *header_out) {
+    return guarded([&]() -> int {
+        if (!rows || !out || !header_out || n == 0) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (n > PTRS_PROBE_MAX_ROWS) { g_err = "too many probe rows"; return PTRS_ERR_INVALID; }
+        if (op >= PROBE_SHADE_NUM_OPS) { g_err = "unknown shade-table probe op"; return PTRS_ERR_INVALID; }
+        if (const char *why = probe_shade_rows_check(nullptr, op, n, rows)) { g_err = why; return PTRS_ERR_INVALID; }
+        if (it > 0xffffu) { g_err = "round out of range"; return PTRS_ERR_INVALID; } // (no render has that many rounds; 12 + 8 it stays far from 2^32)
+        if (!scene || !params) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (const char *why = probe_shade_rows_check(&scene->H, op, n, rows)) { g_err = why; return PTRS_ERR_INVALID; }
+        return with_backend(scene, params, nullptr, [&](HipBackend &be, std::string &err) -> int {
+            RenderSetup u;
+            const PtrsCamera cam{};
+            int rc = render_setup(be, scene->H.max_depth, cam, *params, RenderJob{}, u, err);
+            if (rc != PTRS_OK) return rc;
+            be.sc = scene->sc; be.S = u.S; be.feat = scene_features(scene->H);
+            const ShadeLdsCfg cfg = be.shade_cfg(it);
+            const uint32_t header[PROBE_SHADE_HEADER] = {cfg.sob_lo, cfg.sob_n, cfg.sob_nib, cfg.tri_lds, cfg.n_lights_lds, cfg.marg_li, cfg.pre_li, (uint32_t)be.feat, be.env_presampled_only() ? 1u : 0u, 0u, 0u, 0u};
+            std::memcpy(header_out, header, sizeof(header));
+            DevBuf bi, bo;
+            if ((rc = bi.ensure((size_t)n * PROBE_SHADE_IN * 4)) != PTRS_OK || (rc = bo.ensure((size_t)n * PROBE_SHADE_OUT * 4)) != PTRS_OK) { err = g_err; return rc; }
+            HIPCHK(hipMemcpy(bi.p, rows, (size_t)n * PROBE_SHADE_IN * 4, hipMemcpyHostToDevice));
+            const dim3 grid((n + BLOCK - 1) / BLOCK);
+            if (be.feat & FEAT_INFINITE) hipLaunchKernelGGL(k_probe_shade<true>, grid, dim3(BLOCK), 0, nullptr, be.S, be.sc, cfg, op, n, (const uint32_t *)bi.p, (uint32_t *)bo.p);
+            else hipLaunchKernelGGL(k_probe_shade<false>, grid, dim3(BLOCK), 0, nullptr, be.S, be.sc, cfg, op, n, (const uint32_t *)bi.p, (uint32_t *)bo.p);
+            HIPCHK(hipDeviceSynchronize());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpy(out, bo.p, (size_t)n * PROBE_SHADE_OUT * 4, hipMemcpyDeviceToHost));
+            return PTRS_OK;
+        });
     });
 }
 

@@ -850,6 +850,22 @@ def probe_math(op, rows, device=0):
     return out
 
 
+def probe_shade_tables(scene, params, it, op, rows, device=0):
+    """ptrs_probe_shade_tables: the shade kernels' LDS tables staged as round `it` of a render of `scene` with `params`
+    (a PtrsRenderParams, e.g. PathIntegrator.params(camera)) stages them, then `rows` (n x 12 uint32; floats travel as bit patterns)
+    through that context.  op abi.PROBE_SHADE_SOBOL: row = index lo, index hi, scramble, N, N dimensions -> the N values' bits, column
+    8 the route (abi.SOB_ROUTE_*).  op abi.PROBE_SHADE_ENV: row = u.x, u.y, light -> wi.xyz, pdf, Li.rgb, ok, staged-marginal flag.
+    Returns (header dict with the fields abi.PROBE_SHADE_HEADER, out n x 12 uint32)."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_probe_shade_tables.argtypes = abi.PROBE_SHADE_ARGTYPES
+    rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, abi.PROBE_SHADE_WIDTH)
+    out = np.zeros((rows.shape[0], abi.PROBE_SHADE_WIDTH), dtype=np.uint32)
+    header = np.zeros(12, dtype=np.uint32)
+    _check(L.ptrs_probe_shade_tables(ds.handle, C.byref(params), int(it), int(op), rows.shape[0], C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(header.ctypes.data)))
+    return {k: int(header[i]) for i, k in enumerate(abi.PROBE_SHADE_HEADER)}, out
+
+
 def build_id():
     """ptrs_build_id: hash of the kernel sources and compiler flags the loaded library was built from (build.source_hash)."""
     return load_library().ptrs_build_id().decode()

@@ -140,6 +140,52 @@ def test_texture_and_surface_probes_check_their_arguments(ptrs):
     assert T.twin_texture_probe(ts._h, 0, 1, buf, buf) == 0 and T.twin_surface_probe(ts._h, 0, 1, buf, buf) == 0
 
 
+def test_shade_table_probe_checks_its_arguments(ptrs):
+    """ptrs_probe_shade_tables refuses NULL buffers, no rows, too many rows, an unknown op, a batch size other than 1, 2, 3, 8, a
+    dimension past the tables, a u outside [0, 1), a round above 65535 and a missing scene or parameters before it touches a device (no GPU needed); the
+    binding's op and route lists end where the header file's do."""
+    import numpy as np
+    assert "ptrs_probe_shade_tables" in _declared_functions()
+    L = ptrs.load_library()
+    a = ptrs.abi
+    L.ptrs_probe_shade_tables.argtypes = a.PROBE_SHADE_ARGTYPES
+    prm = a.PtrsRenderParams()
+    prm.width, prm.height, prm.spp, prm.max_depth = 64, 64, 4, 4
+    hdr = (C.c_uint32 * 12)()
+    out = (C.c_uint32 * 12)()
+    row = np.zeros(12, np.uint32)
+    row[3], row[4] = 1, 7
+    rp = lambda r: C.c_void_p(r.ctypes.data)
+    fn = L.ptrs_probe_shade_tables
+    assert fn(None, C.byref(prm), 0, 0, 1, None, out, hdr) != 0 and b"null" in L.ptrs_last_error()         # rows missing
+    assert fn(None, C.byref(prm), 0, 0, 1, rp(row), None, hdr) != 0 and b"null" in L.ptrs_last_error()     # out missing
+    assert fn(None, C.byref(prm), 0, 0, 1, rp(row), out, None) != 0 and b"null" in L.ptrs_last_error()     # header missing
+    assert fn(None, C.byref(prm), 0, 0, 0, rp(row), out, hdr) != 0 and b"null" in L.ptrs_last_error()      # nothing to do
+    assert fn(None, C.byref(prm), 0, 0, (1 << 24) + 1, rp(row), out, hdr) != 0 and b"too many probe rows" in L.ptrs_last_error()
+    for op in (a.PROBE_SHADE_NUM_OPS, 0xffffffff):
+        assert fn(None, C.byref(prm), 0, op, 1, rp(row), out, hdr) != 0 and b"unknown shade-table probe op" in L.ptrs_last_error()
+    for bad_n in (0, 4, 5, 7, 9, 0xffffffff):
+        r = row.copy()
+        r[3] = bad_n
+        assert fn(None, C.byref(prm), 0, 0, 1, rp(r), out, hdr) != 0 and b"1, 2, 3 or 8" in L.ptrs_last_error(), bad_n
+    r = row.copy()
+    r[3], r[4:12] = 8, np.arange(1017, 1025)
+    assert fn(None, C.byref(prm), 0, 0, 1, rp(r), out, hdr) != 0 and b"1024 dimensions" in L.ptrs_last_error()  # the batch's last dimension
+    for u in ((1.0, 0.5), (0.5, 1.0), (-1e-9, 0.5), (np.nan, 0.5)):
+        r = np.zeros(12, np.uint32)
+        r[0:2] = np.array(u, np.float32).view(np.uint32)
+        assert fn(None, C.byref(prm), 0, 1, 1, rp(r), out, hdr) != 0 and b"u outside" in L.ptrs_last_error(), u
+    for bad_it in (0x10000, 0xffffffff):
+        assert fn(None, C.byref(prm), bad_it, 0, 1, rp(row), out, hdr) != 0 and b"round out of range" in L.ptrs_last_error(), bad_it
+    # the rows and the round are in order: what is left is the scene, then the parameters
+    assert fn(None, C.byref(prm), 0, 0, 1, rp(row), out, hdr) != 0 and b"null" in L.ptrs_last_error()
+    assert fn(None, None, 0, 0, 1, rp(row), out, hdr) != 0 and b"null" in L.ptrs_last_error()
+    text = open(os.path.join(ROOT, "pathtracer-rs_amd", "csrc", "pt_probe.h")).read()
+    assert re.search(r"PROBE_SHADE_SOBOL = 0, PROBE_SHADE_ENV = 1, PROBE_SHADE_NUM_OPS\b", text) and a.PROBE_SHADE_NUM_OPS == 2
+    assert re.search(r"PROBE_SHADE_IN = %d, PROBE_SHADE_OUT = %d, PROBE_SHADE_HEADER = 12\b" % (a.PROBE_SHADE_WIDTH, a.PROBE_SHADE_WIDTH), text)
+    assert len(a.PROBE_SHADE_HEADER) <= 12
+
+
 def test_math_probe_checks_its_arguments(ptrs):
     """ptrs_probe_math refuses a missing buffer, no rows, an unknown op and too many rows before it touches a device (no GPU needed);
     the host twin's copy makes the same checks, and the binding's op list ends where the header's does."""
