@@ -49,6 +49,7 @@ struct Options {
     int stack_lds = 8;        // LDS traversal-stack entries per lane for quad-form scenes: 8 (+ tree top cached in LDS) or 16
     int grid_mult = 0;        // queue segments (one wave each) per pass: CUs x 8 x grid_mult; 0 = with several lanes 1 (2 048 on MI355X; 1-4 for scenes whose tree is in HBM, by the paths of a pass: HipBackend::lanes), 8 with one (16 384; Cornell single-lane frame at 4 / 8 / 16: 252 / 216 / 222 ms)
     int grid_pct = 0;         // share of its resident capacity a persistent launch takes: below 100 a kernel leaves wave slots to the kernels of the other pipeline lanes; 0 = 100 (50 with several lanes and a grid_mult given by hand)
+    int segments = 0;         // k >= 1: a pass has at most k queue segments (grid_max = min(grid_max, k), ptrs_trace_bench's likewise): segments of many chunks at sizes a test can render against the oracle; 0 = no cap (test hook, same bits)
     int whole_rounds = 0;     // 1: segments per pass rounded to a whole multiple of the traversal kernels' resident waves (HipBackend::whole_rounds); measured within noise of 0 (exactly CUs x 8 x grid_mult) on Cornell / classroom, 2.5 % slower on colonnade
     int persist = 1;          // queue kernels are launched with the workgroups that fit the machine at once (occupancy x CUs); 0: with 8 per CU, the hardware's maximum (A/B hook)
     int node_form = 0;        // 0 = by size, 2 = quad nodes also for scenes that would fit LDS (test hook)
@@ -75,7 +76,7 @@ Options options() { std::lock_guard<std::mutex> lk(g_opt_mu); return g_opt; }
 struct OptionDesc { const char *name; int Options::*field; int lo, hi; };
 const OptionDesc k_options[] = {
     {"lanes", &Options::lanes, 0, 8}, {"refill", &Options::refill, -1, 64}, {"refill_connect", &Options::refill_connect, -1, 64}, {"stack_lds", &Options::stack_lds, 8, 16},
-    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20}, {"aov_fused_film", &Options::aov_fused_film, 0, 1}, {"denoise_lds", &Options::denoise_lds, -1, 1},
+    {"grid_mult", &Options::grid_mult, 0, 64}, {"persist", &Options::persist, 0, 1}, {"whole_rounds", &Options::whole_rounds, 0, 1}, {"grid_pct", &Options::grid_pct, 0, 100}, {"node_form", &Options::node_form, 0, 2}, {"node_order", &Options::node_order, 0, 1}, {"vote", &Options::vote, -1, 2}, {"shade_lds", &Options::shade_lds, 0, 1}, {"fused_epilogue", &Options::fused_epilogue, 0, 1}, {"fused_resolve", &Options::fused_resolve, 0, 1}, {"workspace_pct", &Options::workspace_pct, 1, 90}, {"peer_copy", &Options::peer_copy, 0, 1}, {"env_presample", &Options::env_presample, 0, 1}, {"deal", &Options::deal, 0, 1}, {"tail", &Options::tail, 0, 1}, {"tail_at", &Options::tail_at, -1, 64}, {"tail_paths", &Options::tail_paths, 0, 1 << 20}, {"aov_fused_film", &Options::aov_fused_film, 0, 1}, {"denoise_lds", &Options::denoise_lds, -1, 1}, {"segments", &Options::segments, 0, 1 << 20},
 };
 
 #define HIPCHK(expr)                                                                                             \
@@ -1731,6 +1732,7 @@ struct HipBackend {
         for (int k = 0; k < 7; ++k) if (ps->H.kinds_present[k]) kinds_mask |= 1u << k;
         grid_max = ps->n_cu * 8 * (opt.grid_mult ? opt.grid_mult : 8);
         if (opt.persist && opt.whole_rounds) grid_max = (int)whole_rounds((uint32_t)grid_max);
+        if (opt.segments >= 1) grid_max = std::min(grid_max, opt.segments); // (test hook: long segments on small passes)
         const size_t n16 = (size_t)cap * 16, n4 = ((size_t)cap + ((size_t)grid_max + 1) * 64) * 4; // queues: G segments of whole 64-entry chunks
         if ((rc = ps->stats.ensure(CNT_NUM * 8)) != PTRS_OK || (rc = ps->table.ensure(1024)) != PTRS_OK) { err = g_err; return rc; }
         if (ps->spill_lane_elems) { // the traversal stacks' global columns: one set per pipeline lane of THIS render (concurrent lanes must not share columns)
@@ -3160,7 +3162,8 @@ int ptrs_trace_bench(PtrsScene *scene, uint32_t n, const float *rays, uint32_t r
         HipBackend be;
         be.ps = scene; be.stream = nullptr; be.opt = scene_options(scene); be.sc = scene->sc;
         be.traversal_policy(scene_trace_features(scene->H));
-        const uint32_t chunks = (n + 63u) / 64u, gmax = (uint32_t)scene->n_cu * 8u * (uint32_t)(be.opt.grid_mult ? be.opt.grid_mult : 8); // (one launch at a time: the single-lane segmentation)
+        const uint32_t chunks = (n + 63u) / 64u, gfull = (uint32_t)scene->n_cu * 8u * (uint32_t)(be.opt.grid_mult ? be.opt.grid_mult : 8); // (one launch at a time: the single-lane segmentation)
+        const uint32_t gmax = be.opt.segments >= 1 ? std::min(gfull, (uint32_t)be.opt.segments) : gfull; // (option `segments`, as in begin)
         const uint32_t G = chunks < gmax ? chunks : gmax, seg_cap = ((chunks + G - 1) / G) * 64u;
         if ((uint64_t)G * seg_cap * 16ull >= (1ull << 32)) { g_err = "ptrs_trace_bench: too many rays for one launch (queue positions are 32-bit byte offsets of 16-byte records: fewer than 2^28)"; return PTRS_ERR_INVALID; }
         be.G = G; be.seg_cap = seg_cap;

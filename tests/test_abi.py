@@ -61,13 +61,16 @@ def test_options_api():
     import importlib
     ptrs = importlib.import_module("pathtracer-rs_amd")
     L = ptrs.load_library()
-    defaults = {"lanes": 0, "grid_pct": 0, "refill": -1, "refill_connect": -1, "vote": -1, "shade_lds": 1, "fused_epilogue": 1, "fused_resolve": 1, "stack_lds": 8, "grid_mult": 0, "persist": 1, "whole_rounds": 0, "node_order": 0, "peer_copy": 1, "env_presample": 1, "node_form": 0, "workspace_pct": 40, "tail": 1, "tail_at": -1, "tail_paths": 0, "deal": 0}
+    defaults = {"lanes": 0, "grid_pct": 0, "refill": -1, "refill_connect": -1, "vote": -1, "shade_lds": 1, "fused_epilogue": 1, "fused_resolve": 1, "stack_lds": 8, "grid_mult": 0, "persist": 1, "whole_rounds": 0, "node_order": 0, "peer_copy": 1, "env_presample": 1, "node_form": 0, "workspace_pct": 40, "tail": 1, "tail_at": -1, "tail_paths": 0, "deal": 0, "segments": 0}
     for k, v in defaults.items():
         assert ptrs.get_option(k) == v, k
     with ptrs.options(lanes=1, vote=0):
         assert ptrs.get_option("lanes") == 1 and ptrs.get_option("vote") == 0
     assert ptrs.get_option("lanes") == 0 and ptrs.get_option("vote") == -1
-    for name, bad in (("lanes", -1), ("lanes", 9), ("workspace_pct", 0), ("vote", 3), ("no_such_option", 1)):
+    with ptrs.options(segments=1 << 20):  # (the test hook that caps a pass's queue segments: 0 .. 2^20)
+        assert ptrs.get_option("segments") == 1 << 20
+    assert ptrs.get_option("segments") == 0
+    for name, bad in (("lanes", -1), ("lanes", 9), ("workspace_pct", 0), ("vote", 3), ("no_such_option", 1), ("segments", -1), ("segments", (1 << 20) + 1)):
         assert L.ptrs_set_option(name.encode(), bad) != 0
         assert L.ptrs_last_error()
     import ctypes as C
