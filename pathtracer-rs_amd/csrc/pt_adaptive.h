@@ -10,9 +10,12 @@
 //                     counts and the test twin all ask here.
 //   ad_row_counts   : the active sample pixels of every sample row (what a pass traces, what the statistics count)
 //   ad_freeze       : the freeze rule of ptrs_render_adaptive, a pure function of one check's tile records
+//   ad_tile_list    : tile flags as a tile render takes them
+//   ad_block_loop   : the loop of ptrs_render_converged and ptrs_render_adaptive over a back end's two hooks (the device's, the twin's)
 // The reference renders every tile with the same sample count and has none of this.
 #pragma once
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "pt_converge.h"
@@ -69,6 +72,57 @@ inline uint32_t ad_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float ta
         next[t] = on; n += on;
     }
     return n;
+}
+
+// What a tile render is given (RenderJob::tile_active, tile_list): the flags as 0 / 1 and the ascending list of the active tiles.
+inline void ad_tile_list(const uint8_t *flags, size_t n_tiles, std::vector<uint8_t> &flags01, std::vector<uint32_t> &list) {
+    flags01.resize(n_tiles); list.clear();
+    for (size_t t = 0; t < n_tiles; ++t) { flags01[t] = flags[t] ? 1 : 0; if (flags[t]) list.push_back((uint32_t)t); }
+}
+
+// ---- the block loop of ptrs_render_converged and ptrs_render_adaptive (no device call: the back end is behind the hooks) -------------
+// The statistics of a run of renders: counts add up, the scene's facts are the last render's, device_bytes is the largest.
+inline void add_stats(PtrsStats &total, const PtrsStats &st) {
+    total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
+    total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
+    total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
+}
+
+// Block by block of cv_schedule's list: the block's first half into the film and the half film, its second half into the film only,
+// then the film's error, a line of the history, and the stop rule.
+//   by_tile = false : every block is a dense render (no tile flags); stops when the largest tile error is below the target
+//   by_tile = true  : a block runs on the tiles still active, ad_freeze takes tiles out behind every check; stops when none is left
+// hooks.render(begin, end, with_half, active, st): samples [begin, end) into the film, and into the half film too when asked, on the
+//   tiles flagged in `active` (n_tiles flags, 0 / 1) or densely (null); st: that render's statistics
+// hooks.measure(sum, records, launches): the film's error -- the summary and, when asked (non-null), the n_tiles tile records; adds
+//   what the measurement launched
+// Both return PTRS_OK or the code the loop returns at once.  res.tiles_x / tiles_y are the caller's; tile_spp[t] = the samples tile t holds.
+template <class Hooks>
+int ad_block_loop(const uint32_t *blocks, uint32_t n_blocks, uint32_t n_tiles, float target, bool by_tile, Hooks &hooks, PtrsAdaptiveResult &res, std::vector<uint32_t> &tile_spp, PtrsStats &total) {
+    std::memset(&res, 0, sizeof(res)); std::memset(&total, 0, sizeof(total));
+    std::vector<uint8_t> active(n_tiles, 1);
+    std::vector<PtrsTileError> records(by_tile ? n_tiles : 0u);
+    tile_spp.assign(n_tiles, 0u);
+    uint32_t n_active = n_tiles;
+    for (uint32_t k = 0; k < n_blocks && !res.converged; ++k) {
+        const uint32_t *b = blocks + 3 * k; // begin, middle, end
+        for (int h = 0; h < 2; ++h) {
+            PtrsStats st;
+            int rc = hooks.render(b[h], b[h + 1], h == 0, by_tile ? active.data() : nullptr, st);
+            if (rc != PTRS_OK) return rc;
+            add_stats(total, st);
+        }
+        for (uint32_t t = 0; t < n_tiles; ++t) if (active[t]) tile_spp[t] = b[2];
+        PtrsFilmErrorSummary sum;
+        int rc = hooks.measure(sum, by_tile ? records.data() : nullptr, total.kernel_launches);
+        if (rc != PTRS_OK) return rc;
+        res.spp_done = b[2];
+        res.history[res.n_checks].spp = b[2]; res.history[res.n_checks].tiles_active = n_active; res.history[res.n_checks].max_tile_error = sum.max_tile_error; ++res.n_checks;
+        res.worst_tile = sum.worst_tile;
+        if (by_tile) n_active = ad_freeze(records.data(), n_tiles, target, active.data(), active.data());
+        res.converged = (by_tile ? n_active == 0u : sum.max_tile_error < target) ? 1u : 0u;
+    }
+    return PTRS_OK;
 }
 
 } // namespace pt

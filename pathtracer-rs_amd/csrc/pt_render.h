@@ -459,12 +459,4 @@ int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_
     return PTRS_OK;
 }
 
-// render_impl's positional form from before RenderJob, forwarded: not called in this tree, kept (deprecated) for twins written against it.
-template <class BE>
-[[deprecated("fill a RenderJob")]] int render_impl(BE &be, const DScene &sc, const HostScene &sc_host_feat, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm, v4 *film, float *samples_out, PtrsStats *stats, std::string &err,
-                const RenderProgress *progress = nullptr, const RayDump *dump = nullptr, const int32_t *single_pixel = nullptr, uint32_t *row_cost = nullptr, const uint32_t *sample_range = nullptr, v4 *film_half = nullptr) {
-    const RenderJob job{film, film_half, samples_out, stats, progress, dump, single_pixel, row_cost, sample_range}; // (RenderJob's member order)
-    return render_impl(be, sc, sc_host_feat, bvh_depth, cam, prm, job, err);
-}
-
 } // namespace pt

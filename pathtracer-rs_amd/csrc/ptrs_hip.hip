@@ -2128,12 +2128,78 @@ int do_render(PtrsScene *ps, const PtrsCamera *cam, const PtrsRenderParams *prm,
     });
 }
 
-// ptrs_render_aov / ptrs_render_aov_device: the checks that need no device, then that there is one
-int aov_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, const void *const *plane_ptrs) {
-    if (!scene || !camera || !params) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
-    for (uint32_t k = 0; k < AOV_PLANES; ++k)
-        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
+// ---- the one check of a render request ---------------------------------------------------------------------------
+// What an entry point takes besides scene, camera and parameters; check_request reads it.  Null / 0: the entry takes no such thing.
+// (Tile flags are only asked not to be null: they come in check_request's `needed`, with whole_film set.)
+struct Request {
+    const void *film = nullptr, *half = nullptr;                                   // a film and its optional half film, or ...
+    bool plane_form = false; uint32_t planes = 0; const void *const *plane_ptrs = nullptr; // ... a plane mask with the planes' pointers
+    const uint32_t *range = nullptr;                                               // a sample range {begin, end}, or ...
+    const uint32_t *min_spp = nullptr;                                             // ... a schedule; with a target, the loop over the films
+    const float *target = nullptr; const void *result = nullptr;                   //     and where its result goes; with tile_spp, the
+    const uint32_t *tile_spp = nullptr;                                            //     samples per tile of an adaptive film
+    const char *whole_film = nullptr; // the name under which a row band is refused (the tile forms, the loops); null: a band is rendered
+    enum { LEFT_TO_SETUP, NO_DEPTH, FULL } params = FULL; // what of the parameters is looked at here (ptrs_render_aov_device: nothing, ptrs_render_aov: not max_depth)
+};
+Request film_request(const void *film, const void *half) { Request q; q.film = film; q.half = half; return q; }
+Request plane_request(uint32_t planes, const void *const *plane_ptrs) { Request q; q.plane_form = true; q.planes = planes; q.plane_ptrs = plane_ptrs; return q; }
+struct Schedule { uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n = 0; };
+
+// Every check an entry point of the family makes before its first device call, each with its message once, then that there is a device.
+// `needed`: the pointers that must not be null beside scene, camera, params and the film of a film form.  Gives the row band to stage and
+// the schedule's blocks.
+int check_request(const PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, std::initializer_list<const void *> needed, const Request &q,
+                  RowBand *band_out = nullptr, Schedule *schedule_out = nullptr) {
+    const auto refuse = [](std::string m) { g_err = std::move(m); return PTRS_ERR_INVALID; };
+    const auto null_argument = [&]() { return refuse("null argument"); };
+    const bool loop = q.target != nullptr; // ptrs_render_converged / ptrs_render_adaptive
+    if (loop && !q.result) return null_argument();
+    if (loop && !(*q.target >= 0.0f && *q.target < PT_INF)) return refuse("render_converged: target_error must be finite and >= 0");
+    bool null = !scene || !camera || !params || (!q.plane_form && !q.film);
+    for (const void *ptr : needed) null = null || !ptr;
+    if (null) return null_argument();
+    if (q.plane_form) {
+        if (q.planes == 0u || (q.planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) return refuse("planes must be a non-empty set of PTRS_AOV_* bits");
+        for (uint32_t k = 0; k < AOV_PLANES; ++k)
+            if ((q.planes & (1u << k)) && (!q.plane_ptrs || !q.plane_ptrs[k])) return refuse("null plane pointer for a requested plane");
+    }
+    const PtrsRenderParams &p = *params;
+    Schedule sched;
+    // (the steps that come at two places of the order below; false: refused, the message is set)
+    const auto params_ok = [&](bool film_too) {
+        if (p.spp > 0 && (!film_too || (p.width > 0 && p.height > 0 && (q.params != Request::FULL || p.max_depth >= 0)))) return true;
+        g_err = "bad render parameters"; return false;
+    };
+    const auto schedule_ok = [&]() { const char *m = cv_schedule(total_spp(p), *q.min_spp, sched.blocks, &sched.n); if (m) g_err = m; return !m; };
+    const auto whole_ok = [&]() {
+        if (!q.whole_film || !(p.row_end > p.row_begin && (p.row_begin != 0 || p.row_end != p.height))) return true;
+        g_err = std::string(q.whole_film) + " renders the whole film (no row band)"; return false;
+    };
+    if (loop) { // the two loops ask about spp, the schedule and the film's size before the rest of the parameters
+        if (!params_ok(false) || !schedule_ok()) return PTRS_ERR_INVALID;
+        if (p.width > 0 && p.height > 0 && (uint64_t)p.width * (uint64_t)p.height >= (1ull << 31)) return refuse("film too large for the error measure");
+        if (!whole_ok()) return PTRS_ERR_INVALID;
+    }
+    if (q.params != Request::LEFT_TO_SETUP && !params_ok(true)) return PTRS_ERR_INVALID;
+    if (q.range && !sample_range_ok(p, q.range[0], q.range[1])) return refuse("sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(p)) + " for these parameters)");
+    if (q.half && q.half == q.film) return refuse("the half film must not be the film");
+    if (!whole_ok()) return PTRS_ERR_INVALID;
+    if (q.tile_spp) { // every tile holds no sample or the samples up to the end of a block
+        if (!schedule_ok()) return PTRS_ERR_INVALID;
+        const uint32_t n_tiles = (uint32_t)ad_tiles_x(p.width) * (uint32_t)ad_tiles_y(p.height);
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            bool ok = q.tile_spp[t] == 0u;
+            for (uint32_t k = 0; k < sched.n && !ok; ++k) ok = q.tile_spp[t] == sched.blocks[3 * k + 2];
+            if (!ok) return refuse("render_aov_adaptive: tile_spp[" + std::to_string(t) + "] = " + std::to_string(q.tile_spp[t]) + " is neither 0 nor the end of a block of the schedule");
+        }
+    }
+    if (q.params != Request::LEFT_TO_SETUP) { // (a whole-film form has passed whole_ok: its band is the film)
+        RowBand band;
+        int rc = row_band(p, band);
+        if (rc != PTRS_OK) return rc;
+        if (band_out) *band_out = band;
+    }
+    if (schedule_out) *schedule_out = sched;
     return require_device();
 }
 
@@ -2153,36 +2219,13 @@ int do_film_error(int32_t W, int32_t H, const v4 *film, const v4 *half, PtrsTile
     HIPCHK(hipStreamSynchronize(stream));
     return PTRS_OK;
 }
-// ptrs_render_range / ptrs_render_range_device / ptrs_render_converged: the checks that need no device, then that there is one
-int range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *film, const void *half, RowBand *band_out = nullptr) {
-    if (!scene || !camera || !params || !film) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
-    if (half && half == film) { g_err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
-    RowBand band;
-    int rc = row_band(*params, band);
-    if (rc != PTRS_OK) return rc;
-    if (band_out) *band_out = band;
-    return require_device();
-}
-
-// ptrs_render_tiles / ptrs_render_tiles_device: the checks that need no device, in the style of the range checks, then that there is one
-int tiles_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const void *tile_active, const void *film, const void *half) {
-    if (!scene || !camera || !params || !film || !tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
-    if (half && half == film) { g_err = "the half film must not be the film"; return PTRS_ERR_INVALID; }
-    if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
-    return require_device();
-}
 // The flags (host memory, non-zero = active) into the scene's device copy as 0 / 1, with the list of the active tiles; `job` gets both and
 // the host copy `flags01`.  n_active = 0: nothing was uploaded, the caller has nothing to render.  (A render has drained its streams when it
 // returns, so nothing reads the scene's copies when the next call overwrites them.)
 int upload_tiles(PtrsScene *ps, const PtrsRenderParams &prm, const uint8_t *flags, std::vector<uint8_t> &flags01, HipJob &job, uint32_t &n_active) {
     const size_t n_tiles = (size_t)ad_tiles_x(prm.width) * (size_t)ad_tiles_y(prm.height);
-    flags01.resize(n_tiles);
     std::vector<uint32_t> list;
-    for (size_t t = 0; t < n_tiles; ++t) { flags01[t] = flags[t] ? 1 : 0; if (flags[t]) list.push_back((uint32_t)t); }
+    ad_tile_list(flags, n_tiles, flags01, list);
     n_active = (uint32_t)list.size();
     if (list.empty()) return PTRS_OK;
     int rc;
@@ -2192,33 +2235,26 @@ int upload_tiles(PtrsScene *ps, const PtrsRenderParams &prm, const uint8_t *flag
     job.tile_active = (const uint8_t *)ps->ad_flags.p; job.tile_active_host = flags01.data(); job.tile_list = (const uint32_t *)ps->ad_list.p; job.n_tile_list = n_active;
     return PTRS_OK;
 }
-
-// ptrs_render_aov_range / ptrs_render_aov_tiles and their device forms: ptrs_render_aov's checks, then ptrs_render_range's (the tile
-// form: ptrs_render_tiles') with their messages, then that there is a device
-int aov_range_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes, const void *const *plane_ptrs,
-                         bool tile_form, RowBand *band_out) {
-    if (!scene || !camera || !params) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
-    for (uint32_t k = 0; k < AOV_PLANES; ++k)
-        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
-    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-    if (!sample_range_ok(*params, sample_begin, sample_end)) { g_err = "sample range: need sample_begin < sample_end <= spp (" + std::to_string(total_spp(*params)) + " for these parameters)"; return PTRS_ERR_INVALID; }
-    if (tile_form && params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
-    RowBand band;
-    int rc = row_band(*params, band);
-    if (rc != PTRS_OK) return rc;
-    if (band_out) *band_out = band;
-    return require_device();
+// The four tile entry points, behind their checks: the scene's device, the flags up; nothing = true: no tile is active -- no launch, the
+// films or planes stay, the statistics are zeros and the entry returns.
+int begin_tiles(PtrsScene *ps, const PtrsRenderParams &prm, const uint8_t *flags, std::vector<uint8_t> &flags01, HipJob &job, PtrsStats *stats, bool &nothing) {
+    HIPCHK(hipSetDevice(ps->device));
+    uint32_t n_active = 0;
+    int rc = upload_tiles(ps, prm, flags, flags01, job, n_active);
+    nothing = rc == PTRS_OK && n_active == 0;
+    if (nothing && stats) std::memset(stats, 0, sizeof(*stats));
+    return rc;
 }
+
 DAovFilm device_planes(uint32_t planes, void *const *ptrs) {
     DAovFilm F;
     for (uint32_t k = 0; k < AOV_PLANES; ++k) F.plane[k] = (planes & (1u << k)) ? (v4 *)ptrs[k] : nullptr;
     return F;
 }
-// The host form of the calls above: the band of every plane asked for travels to the scene's device copies, run(films, samples) does
-// the device's part, the band travels back.  The sample export starts from the caller's buffer: the entries the call does not write
-// (outside the range, inactive sample pixels) keep what they held.
-template <class Run> int aov_host_planes(PtrsScene *scene, const PtrsRenderParams *params, const RowBand &band, uint32_t planes, PtrsFilmPixel *const *planes_inout, float *sample_aov, Run run) {
+// The host form of the plane calls: the band of every plane asked for travels to the scene's device copies, run(films, samples) does
+// the device's part, the band travels back.  The sample export starts from zeros; with a sample range (`ranged`) it starts from the
+// caller's buffer: the entries the call does not write (outside the range, inactive sample pixels) keep what they held.
+template <class Run> int aov_host_planes(PtrsScene *scene, const PtrsRenderParams *params, const RowBand &band, uint32_t planes, PtrsFilmPixel *const *planes_inout, float *sample_aov, bool ranged, Run run) {
     HIPCHK(hipSetDevice(scene->device));
     int rc;
     DAovFilm F;
@@ -2231,7 +2267,8 @@ template <class Run> int aov_host_planes(PtrsScene *scene, const PtrsRenderParam
     const size_t sbytes = sample_aov ? sample_buffer_bytes(*params, PTRS_AOV_SAMPLE_FLOATS) : 0;
     if (sample_aov) {
         if ((rc = scene->aov_samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy(scene->aov_samples_tmp.p, sample_aov, sbytes, hipMemcpyHostToDevice));
+        if (ranged) HIPCHK(hipMemcpy(scene->aov_samples_tmp.p, sample_aov, sbytes, hipMemcpyHostToDevice));
+        else HIPCHK(hipMemset(scene->aov_samples_tmp.p, 0, sbytes));
     }
     if ((rc = run(F, sample_aov ? (float *)scene->aov_samples_tmp.p : nullptr)) != PTRS_OK) return rc;
     for (uint32_t k = 0; k < AOV_PLANES; ++k)
@@ -2243,37 +2280,19 @@ template <class Run> int aov_host_planes(PtrsScene *scene, const PtrsRenderParam
 // ptrs_render_aov_adaptive: the planes of a film whose tile t holds tile_spp[t] samples of the schedule.  Block k = [begin_k, end_k) runs
 // on the tiles with tile_spp[t] >= end_k; consecutive blocks with the same tile set are one run, a block without a tile is none.
 struct AovRun { uint32_t begin, end; std::vector<uint8_t> tiles; };
-int aov_adaptive_check_args(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes, const void *const *plane_ptrs,
-                            std::vector<AovRun> &runs, RowBand *band_out) {
-    if (!scene || !camera || !params || !tile_spp) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    if (planes == 0u || (planes & ~(uint32_t)(PTRS_AOV_ALBEDO | PTRS_AOV_NORMAL | PTRS_AOV_DEPTH)) != 0u) { g_err = "planes must be a non-empty set of PTRS_AOV_* bits"; return PTRS_ERR_INVALID; }
-    for (uint32_t k = 0; k < AOV_PLANES; ++k)
-        if ((planes & (1u << k)) && (!plane_ptrs || !plane_ptrs[k])) { g_err = "null plane pointer for a requested plane"; return PTRS_ERR_INVALID; }
-    if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->max_depth < 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-    if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_tiles renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
-    uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
-    if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
-    const uint32_t n_tiles = (uint32_t)ad_tiles_x(params->width) * (uint32_t)ad_tiles_y(params->height);
-    for (uint32_t t = 0; t < n_tiles; ++t) {
-        bool ok = tile_spp[t] == 0u;
-        for (uint32_t k = 0; k < n_blocks && !ok; ++k) ok = tile_spp[t] == blocks[3 * k + 2];
-        if (!ok) { g_err = "render_aov_adaptive: tile_spp[" + std::to_string(t) + "] = " + std::to_string(tile_spp[t]) + " is neither 0 nor the end of a block of the schedule"; return PTRS_ERR_INVALID; }
-    }
-    runs.clear();
-    for (uint32_t k = 0; k < n_blocks; ++k) {
+std::vector<AovRun> aov_adaptive_runs(const PtrsRenderParams &prm, const Schedule &sched, const uint32_t *tile_spp) {
+    const uint32_t n_tiles = (uint32_t)ad_tiles_x(prm.width) * (uint32_t)ad_tiles_y(prm.height);
+    std::vector<AovRun> runs;
+    for (uint32_t k = 0; k < sched.n; ++k) {
+        const uint32_t *b = sched.blocks + 3 * k;
         std::vector<uint8_t> set(n_tiles);
         bool any = false;
-        for (uint32_t t = 0; t < n_tiles; ++t) { set[t] = tile_spp[t] >= blocks[3 * k + 2] ? 1 : 0; any = any || set[t]; }
+        for (uint32_t t = 0; t < n_tiles; ++t) { set[t] = tile_spp[t] >= b[2] ? 1 : 0; any = any || set[t]; }
         if (!any) continue;
-        if (!runs.empty() && runs.back().end == blocks[3 * k] && runs.back().tiles == set) runs.back().end = blocks[3 * k + 2];
-        else runs.push_back(AovRun{blocks[3 * k], blocks[3 * k + 2], std::move(set)});
+        if (!runs.empty() && runs.back().end == b[0] && runs.back().tiles == set) runs.back().end = b[2];
+        else runs.push_back(AovRun{b[0], b[2], std::move(set)});
     }
-    RowBand band;
-    PtrsRenderParams whole = *params; whole.row_begin = 0; whole.row_end = 0;
-    int rc = row_band(whole, band);
-    if (rc != PTRS_OK) return rc;
-    if (band_out) *band_out = band;
-    return require_device();
+    return runs;
 }
 int do_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, const std::vector<AovRun> &runs, uint32_t planes, const DAovFilm &F, hipStream_t stream, PtrsStats *stats) {
     const auto t_begin = std::chrono::steady_clock::now();
@@ -2288,10 +2307,59 @@ int do_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const Ptr
         if (rc != PTRS_OK) return rc;
         PtrsStats st;
         if ((rc = do_render_aov(scene, camera, params, planes, F, nullptr, stream, &st, job)) != PTRS_OK) return rc;
-        total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
-        total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
-        total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
+        add_stats(total, st);
     }
+    total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = total;
+    return PTRS_OK;
+}
+
+// ad_block_loop's hooks over the scene's device films (film_tmp, half_tmp) and error buffers (cv_tiles, cv_summary)
+struct DeviceFilmHooks {
+    PtrsScene *ps; const PtrsCamera *cam; const PtrsRenderParams *prm; uint32_t n_tiles;
+    std::vector<uint8_t> flags01; HipJob tiles; // the tile set on the device: the flags travel when they have changed (once per block)
+    int render(uint32_t begin, uint32_t end, bool with_half, const uint8_t *active, PtrsStats &st) {
+        if (active && (flags01.empty() || !std::equal(flags01.begin(), flags01.end(), active))) {
+            uint32_t n_up = 0;
+            int rc = upload_tiles(ps, *prm, active, flags01, tiles, n_up);
+            if (rc != PTRS_OK) return rc;
+        }
+        const uint32_t range[2] = {begin, end};
+        HipJob job = tiles; // (the dense form: no tile field is set)
+        job.film = (v4 *)ps->film_tmp.p; job.film_half = with_half ? (v4 *)ps->half_tmp.p : nullptr; job.sample_range = range; job.stats = &st;
+        return do_render(ps, cam, prm, job);
+    }
+    int measure(PtrsFilmErrorSummary &sum, PtrsTileError *records, uint64_t &launches) {
+        int rc = do_film_error(prm->width, prm->height, (const v4 *)ps->film_tmp.p, (const v4 *)ps->half_tmp.p, (PtrsTileError *)ps->cv_tiles.p, (PtrsFilmErrorSummary *)ps->cv_summary.p, nullptr, &sum);
+        if (rc != PTRS_OK) return rc;
+        if (records) HIPCHK(hipMemcpy(records, ps->cv_tiles.p, (size_t)n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost)); // (8 bytes per tile: what the freeze rule reads)
+        launches += 2;
+        return PTRS_OK;
+    }
+};
+// ptrs_render_converged (by_tile = false) and ptrs_render_adaptive: check, the scene's buffers with the caller's film and a cleared half
+// film in them, ad_block_loop, the films back
+int render_blocks(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp, bool by_tile,
+                  PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, const void *result_out, PtrsAdaptiveResult &res, std::vector<uint32_t> &tile_spp, PtrsStats *stats) {
+    Request q = film_request(film_inout, film_half_out);
+    q.min_spp = &min_spp; q.target = &target_error; q.result = result_out; q.whole_film = "render_converged";
+    Schedule sched;
+    int rc = check_request(scene, camera, params, {}, q, nullptr, &sched);
+    if (rc != PTRS_OK) return rc;
+    const auto t_begin = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(scene->device));
+    const size_t bytes = (size_t)params->width * (size_t)params->height * sizeof(PtrsFilmPixel);
+    const uint32_t tiles_x = (uint32_t)ad_tiles_x(params->width), tiles_y = (uint32_t)ad_tiles_y(params->height), n_tiles = tiles_x * tiles_y;
+    if ((rc = scene->film_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->half_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->cv_tiles.ensure((size_t)n_tiles * sizeof(PtrsTileError))) != PTRS_OK ||
+        (rc = scene->cv_summary.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
+    HIPCHK(hipMemcpy(scene->film_tmp.p, film_inout, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(scene->half_tmp.p, 0, bytes));
+    DeviceFilmHooks hooks{scene, camera, params, n_tiles, {}, {}};
+    PtrsStats total;
+    if ((rc = ad_block_loop(sched.blocks, sched.n, n_tiles, target_error, by_tile, hooks, res, tile_spp, total)) != PTRS_OK) return rc;
+    res.tiles_x = tiles_x; res.tiles_y = tiles_y;
+    HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
+    if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
     total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = total;
     return PTRS_OK;
@@ -2513,41 +2581,23 @@ int ptrs_render_samples(PtrsScene *scene, const PtrsCamera *camera, const PtrsRe
 int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES],
                            float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = aov_check_args(scene, camera, params, planes, (const void *const *)planes_inout_device);
+        Request q = plane_request(planes, (const void *const *)planes_inout_device);
+        q.params = Request::LEFT_TO_SETUP;
+        int rc = check_request(scene, camera, params, {}, q);
         if (rc != PTRS_OK) return rc;
-        DAovFilm F;
-        for (uint32_t k = 0; k < AOV_PLANES; ++k) F.plane[k] = (planes & (1u << k)) ? (v4 *)planes_inout_device[k] : nullptr;
-        return do_render_aov(scene, camera, params, planes, F, sample_aov_device, (hipStream_t)hip_stream, stats);
+        return do_render_aov(scene, camera, params, planes, device_planes(planes, planes_inout_device), sample_aov_device, (hipStream_t)hip_stream, stats);
     });
 }
 
 int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES],
                     float *sample_aov, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = aov_check_args(scene, camera, params, planes, (const void *const *)planes_inout);
-        if (rc != PTRS_OK) return rc;
-        if (params->width <= 0 || params->height <= 0 || params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-        HIPCHK(hipSetDevice(scene->device));
+        Request q = plane_request(planes, (const void *const *)planes_inout);
+        q.params = Request::NO_DEPTH;
         RowBand band;
-        if ((rc = row_band(*params, band)) != PTRS_OK) return rc;
-        DAovFilm F;
-        for (uint32_t k = 0; k < AOV_PLANES; ++k) {
-            F.plane[k] = nullptr;
-            if (!(planes & (1u << k))) continue;
-            if ((rc = stage_in(scene->aov_film_tmp[k], *params, band, planes_inout[k])) != PTRS_OK) return rc;
-            F.plane[k] = (v4 *)scene->aov_film_tmp[k].p;
-        }
-        const size_t sbytes = sample_aov ? sample_buffer_bytes(*params, PTRS_AOV_SAMPLE_FLOATS) : 0;
-        if (sample_aov) {
-            if ((rc = scene->aov_samples_tmp.ensure(sbytes)) != PTRS_OK) return rc;
-            HIPCHK(hipMemset(scene->aov_samples_tmp.p, 0, sbytes));
-        }
-        rc = do_render_aov(scene, camera, params, planes, F, sample_aov ? (float *)scene->aov_samples_tmp.p : nullptr, nullptr, stats);
+        int rc = check_request(scene, camera, params, {}, q, &band);
         if (rc != PTRS_OK) return rc;
-        for (uint32_t k = 0; k < AOV_PLANES; ++k)
-            if (F.plane[k] && (rc = stage_out(scene->aov_film_tmp[k], band, planes_inout[k])) != PTRS_OK) return rc;
-        if (sample_aov) HIPCHK(hipMemcpy(sample_aov, scene->aov_samples_tmp.p, sbytes, hipMemcpyDeviceToHost));
-        return PTRS_OK;
+        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, false, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats); });
     });
 }
 
@@ -2604,9 +2654,11 @@ int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixe
 int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
                              void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout_device, film_half_inout_device);
-        if (rc != PTRS_OK) return rc;
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = film_request(film_inout_device, film_half_inout_device);
+        q.range = range;
+        int rc = check_request(scene, camera, params, {}, q);
+        if (rc != PTRS_OK) return rc;
         HipJob job;
         job.film = (v4 *)film_inout_device; job.film_half = (v4 *)film_half_inout_device; job.sample_range = range; job.stream = (hipStream_t)hip_stream; job.stats = stats;
         return do_render(scene, camera, params, job);
@@ -2616,11 +2668,13 @@ int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const P
 int ptrs_render_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
                       PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
     return guarded([&]() -> int {
+        const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = film_request(film_inout, film_half_inout);
+        q.range = range;
         RowBand band;
-        int rc = range_check_args(scene, camera, params, sample_begin, sample_end, film_inout, film_half_inout, &band);
+        int rc = check_request(scene, camera, params, {}, q, &band);
         if (rc != PTRS_OK) return rc;
         HIPCHK(hipSetDevice(scene->device));
-        const uint32_t range[2] = {sample_begin, sample_end};
         HipJob job;
         job.sample_range = range; job.stats = stats;
         return render_host_films(scene, camera, params, band, job, film_inout, film_half_inout, sample_rgb);
@@ -2666,52 +2720,12 @@ int ptrs_converge_schedule(uint32_t spp, uint32_t min_spp, uint32_t *blocks_out,
 int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
                           PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, PtrsConvergeResult *result_out, PtrsStats *stats) {
     return guarded([&]() -> int {
-        if (!result_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        if (!(target_error >= 0.0f && target_error < PT_INF)) { g_err = "render_converged: target_error must be finite and >= 0"; return PTRS_ERR_INVALID; }
-        uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
-        if (!scene || !camera || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        if (params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-        if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
-        if (params->width > 0 && params->height > 0 && (uint64_t)params->width * (uint64_t)params->height >= (1ull << 31)) { g_err = "film too large for the error measure"; return PTRS_ERR_INVALID; }
-        if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_converged renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
-        int rc = range_check_args(scene, camera, params, 0u, min_spp, film_inout, film_half_out);
+        PtrsAdaptiveResult res; std::vector<uint32_t> tile_spp;
+        int rc = render_blocks(scene, camera, params, target_error, min_spp, false, film_inout, film_half_out, result_out, res, tile_spp, stats);
         if (rc != PTRS_OK) return rc;
-        const auto t_begin = std::chrono::steady_clock::now();
-        HIPCHK(hipSetDevice(scene->device));
-        const int32_t W = params->width, H = params->height;
-        const size_t bytes = (size_t)W * (size_t)H * sizeof(PtrsFilmPixel);
-        const size_t n_tiles = (size_t)(((uint32_t)W + CV_TILE - 1u) / CV_TILE) * (size_t)(((uint32_t)H + CV_TILE - 1u) / CV_TILE);
-        if ((rc = scene->film_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->half_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->cv_tiles.ensure(n_tiles * sizeof(PtrsTileError))) != PTRS_OK ||
-            (rc = scene->cv_summary.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy(scene->film_tmp.p, film_inout, bytes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(scene->half_tmp.p, 0, bytes));
-        PtrsConvergeResult res; std::memset(&res, 0, sizeof(res));
-        PtrsStats total; std::memset(&total, 0, sizeof(total));
-        for (uint32_t k = 0; k < n_blocks; ++k) {
-            const uint32_t parts[2][2] = {{blocks[3 * k], blocks[3 * k + 1]}, {blocks[3 * k + 1], blocks[3 * k + 2]}};
-            for (int h = 0; h < 2; ++h) { // the block's first half into both films, its second half into the film only
-                PtrsStats st;
-                HipJob job;
-                job.film = (v4 *)scene->film_tmp.p; job.film_half = h == 0 ? (v4 *)scene->half_tmp.p : nullptr; job.sample_range = parts[h]; job.stats = &st;
-                if ((rc = do_render(scene, camera, params, job)) != PTRS_OK) return rc;
-                total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
-                total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
-                total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
-            }
-            PtrsFilmErrorSummary sum;
-            if ((rc = do_film_error(W, H, (const v4 *)scene->film_tmp.p, (const v4 *)scene->half_tmp.p, (PtrsTileError *)scene->cv_tiles.p, (PtrsFilmErrorSummary *)scene->cv_summary.p, nullptr, &sum)) != PTRS_OK) return rc;
-            total.kernel_launches += 2;
-            res.spp_done = blocks[3 * k + 2];
-            res.history[res.n_checks].spp = res.spp_done; res.history[res.n_checks].max_tile_error = sum.max_tile_error; ++res.n_checks;
-            res.worst_tile = sum.worst_tile;
-            res.converged = sum.max_tile_error < target_error ? 1u : 0u;
-            if (res.converged) break;
-        }
-        HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
-        if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
-        *result_out = res;
-        total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        if (stats) *stats = total;
+        std::memset(result_out, 0, sizeof(*result_out));
+        result_out->spp_done = res.spp_done; result_out->converged = res.converged; result_out->n_checks = res.n_checks; result_out->worst_tile = res.worst_tile;
+        for (uint32_t i = 0; i < res.n_checks; ++i) { result_out->history[i].spp = res.history[i].spp; result_out->history[i].max_tile_error = res.history[i].max_tile_error; }
         return PTRS_OK;
     });
 }
@@ -2720,15 +2734,15 @@ int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
 int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                              void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = tiles_check_args(scene, camera, params, sample_begin, sample_end, tile_active, film_inout_device, film_half_inout_device);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipSetDevice(scene->device));
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = film_request(film_inout_device, film_half_inout_device);
+        q.range = range; q.whole_film = "render_tiles";
+        int rc = check_request(scene, camera, params, {tile_active}, q);
+        if (rc != PTRS_OK) return rc;
         HipJob job;
         job.film = (v4 *)film_inout_device; job.film_half = (v4 *)film_half_inout_device; job.sample_range = range; job.stream = (hipStream_t)hip_stream; job.stats = stats;
-        std::vector<uint8_t> flags01; uint32_t n_active = 0;
-        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
-        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; } // no tile is active: no launch, the films stay
+        std::vector<uint8_t> flags01; bool nothing = false;
+        if ((rc = begin_tiles(scene, *params, tile_active, flags01, job, stats, nothing)) != PTRS_OK || nothing) return rc;
         return do_render(scene, camera, params, job);
     });
 }
@@ -2736,18 +2750,16 @@ int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const P
 int ptrs_render_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                       PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = tiles_check_args(scene, camera, params, sample_begin, sample_end, tile_active, film_inout, film_half_inout);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipSetDevice(scene->device));
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = film_request(film_inout, film_half_inout);
+        q.range = range; q.whole_film = "render_tiles";
+        RowBand band;
+        int rc = check_request(scene, camera, params, {tile_active}, q, &band);
+        if (rc != PTRS_OK) return rc;
         HipJob job;
         job.sample_range = range; job.stats = stats;
-        std::vector<uint8_t> flags01; uint32_t n_active = 0;
-        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
-        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
-        RowBand band;
-        PtrsRenderParams whole = *params; whole.row_begin = 0; whole.row_end = 0;
-        if ((rc = row_band(whole, band)) != PTRS_OK) return rc;
+        std::vector<uint8_t> flags01; bool nothing = false;
+        if ((rc = begin_tiles(scene, *params, tile_active, flags01, job, stats, nothing)) != PTRS_OK || nothing) return rc;
         return render_host_films(scene, camera, params, band, job, film_inout, film_half_inout, sample_rgb);
     });
 }
@@ -2761,63 +2773,11 @@ int ptrs_adaptive_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float tar
 int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
                          PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, uint32_t *tile_spp_out, PtrsAdaptiveResult *result_out, PtrsStats *stats) {
     return guarded([&]() -> int {
-        // (ptrs_render_converged's checks, with its messages)
-        if (!result_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        if (!(target_error >= 0.0f && target_error < PT_INF)) { g_err = "render_converged: target_error must be finite and >= 0"; return PTRS_ERR_INVALID; }
-        uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
-        if (!scene || !camera || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        if (params->spp <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
-        if (const char *m = cv_schedule(total_spp(*params), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
-        if (params->width > 0 && params->height > 0 && (uint64_t)params->width * (uint64_t)params->height >= (1ull << 31)) { g_err = "film too large for the error measure"; return PTRS_ERR_INVALID; }
-        if (params->row_end > params->row_begin && (params->row_begin != 0 || params->row_end != params->height)) { g_err = "render_converged renders the whole film (no row band)"; return PTRS_ERR_INVALID; }
-        int rc = range_check_args(scene, camera, params, 0u, min_spp, film_inout, film_half_out);
+        PtrsAdaptiveResult res; std::vector<uint32_t> tile_spp;
+        int rc = render_blocks(scene, camera, params, target_error, min_spp, true, film_inout, film_half_out, result_out, res, tile_spp, stats);
         if (rc != PTRS_OK) return rc;
-        const auto t_begin = std::chrono::steady_clock::now();
-        HIPCHK(hipSetDevice(scene->device));
-        const int32_t W = params->width, H = params->height;
-        const size_t bytes = (size_t)W * (size_t)H * sizeof(PtrsFilmPixel);
-        const uint32_t tiles_x = (uint32_t)ad_tiles_x(W), tiles_y = (uint32_t)ad_tiles_y(H), n_tiles = tiles_x * tiles_y;
-        if ((rc = scene->film_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->half_tmp.ensure(bytes)) != PTRS_OK || (rc = scene->cv_tiles.ensure((size_t)n_tiles * sizeof(PtrsTileError))) != PTRS_OK ||
-            (rc = scene->cv_summary.ensure(sizeof(PtrsFilmErrorSummary))) != PTRS_OK) return rc;
-        HIPCHK(hipMemcpy(scene->film_tmp.p, film_inout, bytes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(scene->half_tmp.p, 0, bytes));
-        PtrsAdaptiveResult res; std::memset(&res, 0, sizeof(res));
-        res.tiles_x = tiles_x; res.tiles_y = tiles_y;
-        PtrsStats total; std::memset(&total, 0, sizeof(total));
-        std::vector<uint8_t> active(n_tiles, 1), flags01;
-        std::vector<uint32_t> tile_spp(n_tiles, 0u);
-        std::vector<PtrsTileError> records(n_tiles);
-        uint32_t n_active = n_tiles;
-        for (uint32_t k = 0; k < n_blocks && n_active != 0; ++k) {
-            const uint32_t parts[2][2] = {{blocks[3 * k], blocks[3 * k + 1]}, {blocks[3 * k + 1], blocks[3 * k + 2]}};
-            HipJob tiles_job; uint32_t n_up = 0;
-            if ((rc = upload_tiles(scene, *params, active.data(), flags01, tiles_job, n_up)) != PTRS_OK) return rc;
-            for (int h = 0; h < 2; ++h) { // the block's first half into both films, its second half into the film only; both on the block's active tiles
-                PtrsStats st;
-                HipJob job = tiles_job;
-                job.film = (v4 *)scene->film_tmp.p; job.film_half = h == 0 ? (v4 *)scene->half_tmp.p : nullptr; job.sample_range = parts[h]; job.stats = &st;
-                if ((rc = do_render(scene, camera, params, job)) != PTRS_OK) return rc;
-                total.samples += st.samples; total.rays_extension += st.rays_extension; total.rays_shadow += st.rays_shadow; total.rays_mis += st.rays_mis;
-                total.passes += st.passes; total.kernel_launches += st.kernel_launches; total.trace_launches += st.trace_launches; total.film_launches += st.film_launches;
-                total.bvh_nodes = st.bvh_nodes; total.bvh_max_depth = st.bvh_max_depth; total.device_bytes = std::max(total.device_bytes, st.device_bytes); total.lanes = st.lanes;
-            }
-            for (uint32_t t = 0; t < n_tiles; ++t) if (active[t]) tile_spp[t] = blocks[3 * k + 2];
-            PtrsFilmErrorSummary sum;
-            if ((rc = do_film_error(W, H, (const v4 *)scene->film_tmp.p, (const v4 *)scene->half_tmp.p, (PtrsTileError *)scene->cv_tiles.p, (PtrsFilmErrorSummary *)scene->cv_summary.p, nullptr, &sum)) != PTRS_OK) return rc;
-            HIPCHK(hipMemcpy(records.data(), scene->cv_tiles.p, (size_t)n_tiles * sizeof(PtrsTileError), hipMemcpyDeviceToHost)); // (8 bytes per tile: what the freeze rule reads)
-            total.kernel_launches += 2;
-            res.spp_done = blocks[3 * k + 2];
-            res.history[res.n_checks].spp = res.spp_done; res.history[res.n_checks].tiles_active = n_active; res.history[res.n_checks].max_tile_error = sum.max_tile_error; ++res.n_checks;
-            res.worst_tile = sum.worst_tile;
-            n_active = ad_freeze(records.data(), n_tiles, target_error, active.data(), active.data());
-            res.converged = n_active == 0u ? 1u : 0u;
-        }
-        HIPCHK(hipMemcpy(film_inout, scene->film_tmp.p, bytes, hipMemcpyDeviceToHost));
-        if (film_half_out) HIPCHK(hipMemcpy(film_half_out, scene->half_tmp.p, bytes, hipMemcpyDeviceToHost));
-        if (tile_spp_out) std::memcpy(tile_spp_out, tile_spp.data(), (size_t)n_tiles * 4);
+        if (tile_spp_out) std::memcpy(tile_spp_out, tile_spp.data(), tile_spp.size() * 4);
         *result_out = res;
-        total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        if (stats) *stats = total;
         return PTRS_OK;
     });
 }
@@ -2826,9 +2786,11 @@ int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsR
 int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
                                  void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout_device, false, nullptr);
-        if (rc != PTRS_OK) return rc;
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = plane_request(planes, (const void *const *)planes_inout_device);
+        q.range = range;
+        int rc = check_request(scene, camera, params, {}, q);
+        if (rc != PTRS_OK) return rc;
         RenderJob job;
         job.sample_range = range;
         return do_render_aov(scene, camera, params, planes, device_planes(planes, planes_inout_device), sample_aov_device, (hipStream_t)hip_stream, stats, job);
@@ -2838,29 +2800,30 @@ int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, con
 int ptrs_render_aov_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
                           PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
     return guarded([&]() -> int {
-        RowBand band;
-        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout, false, &band);
-        if (rc != PTRS_OK) return rc;
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = plane_request(planes, (const void *const *)planes_inout);
+        q.range = range;
+        RowBand band;
+        int rc = check_request(scene, camera, params, {}, q, &band);
+        if (rc != PTRS_OK) return rc;
         RenderJob job;
         job.sample_range = range;
-        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
+        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, true, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
     });
 }
 
 int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                                  uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        if (!tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout_device, true, nullptr);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipSetDevice(scene->device));
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = plane_request(planes, (const void *const *)planes_inout_device);
+        q.range = range; q.whole_film = "render_tiles";
+        int rc = check_request(scene, camera, params, {tile_active}, q);
+        if (rc != PTRS_OK) return rc;
         HipJob job;
         job.sample_range = range;
-        std::vector<uint8_t> flags01; uint32_t n_active = 0;
-        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
-        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; } // no tile is active: no launch, the planes stay
+        std::vector<uint8_t> flags01; bool nothing = false;
+        if ((rc = begin_tiles(scene, *params, tile_active, flags01, job, stats, nothing)) != PTRS_OK || nothing) return rc;
         return do_render_aov(scene, camera, params, planes, device_planes(planes, planes_inout_device), sample_aov_device, (hipStream_t)hip_stream, stats, job);
     });
 }
@@ -2868,40 +2831,43 @@ int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, con
 int ptrs_render_aov_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                           uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
     return guarded([&]() -> int {
-        if (!tile_active) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-        RowBand band;
-        int rc = aov_range_check_args(scene, camera, params, sample_begin, sample_end, planes, (const void *const *)planes_inout, true, &band);
-        if (rc != PTRS_OK) return rc;
-        HIPCHK(hipSetDevice(scene->device));
         const uint32_t range[2] = {sample_begin, sample_end};
+        Request q = plane_request(planes, (const void *const *)planes_inout);
+        q.range = range; q.whole_film = "render_tiles";
+        RowBand band;
+        int rc = check_request(scene, camera, params, {tile_active}, q, &band);
+        if (rc != PTRS_OK) return rc;
         HipJob job;
         job.sample_range = range;
-        std::vector<uint8_t> flags01; uint32_t n_active = 0;
-        if ((rc = upload_tiles(scene, *params, tile_active, flags01, job, n_active)) != PTRS_OK) return rc;
-        if (n_active == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
-        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
+        std::vector<uint8_t> flags01; bool nothing = false;
+        if ((rc = begin_tiles(scene, *params, tile_active, flags01, job, stats, nothing)) != PTRS_OK || nothing) return rc;
+        return aov_host_planes(scene, params, band, planes, planes_inout, sample_aov, true, [&](const DAovFilm &F, float *samples_dev) { return do_render_aov(scene, camera, params, planes, F, samples_dev, nullptr, stats, job); });
     });
 }
 
 int ptrs_render_aov_adaptive_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
                                     void *const planes_inout_device[PTRS_AOV_PLANES], void *hip_stream, PtrsStats *stats) {
     return guarded([&]() -> int {
-        std::vector<AovRun> runs;
-        int rc = aov_adaptive_check_args(scene, camera, params, min_spp, tile_spp, planes, (const void *const *)planes_inout_device, runs, nullptr);
+        Request q = plane_request(planes, (const void *const *)planes_inout_device);
+        q.min_spp = &min_spp; q.tile_spp = tile_spp; q.whole_film = "render_tiles";
+        Schedule sched;
+        int rc = check_request(scene, camera, params, {tile_spp}, q, nullptr, &sched);
         if (rc != PTRS_OK) return rc;
-        return do_render_aov_adaptive(scene, camera, params, runs, planes, device_planes(planes, planes_inout_device), (hipStream_t)hip_stream, stats);
+        return do_render_aov_adaptive(scene, camera, params, aov_adaptive_runs(*params, sched, tile_spp), planes, device_planes(planes, planes_inout_device), (hipStream_t)hip_stream, stats);
     });
 }
 
 int ptrs_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
                              PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], PtrsStats *stats) {
     return guarded([&]() -> int {
-        std::vector<AovRun> runs;
-        RowBand band;
-        int rc = aov_adaptive_check_args(scene, camera, params, min_spp, tile_spp, planes, (const void *const *)planes_inout, runs, &band);
+        Request q = plane_request(planes, (const void *const *)planes_inout);
+        q.min_spp = &min_spp; q.tile_spp = tile_spp; q.whole_film = "render_tiles";
+        Schedule sched; RowBand band;
+        int rc = check_request(scene, camera, params, {tile_spp}, q, &band, &sched);
         if (rc != PTRS_OK) return rc;
+        const std::vector<AovRun> runs = aov_adaptive_runs(*params, sched, tile_spp);
         // (the planes travel once: the blocks run on the device copies)
-        return aov_host_planes(scene, params, band, planes, planes_inout, nullptr, [&](const DAovFilm &F, float *) { return do_render_aov_adaptive(scene, camera, params, runs, planes, F, nullptr, stats); });
+        return aov_host_planes(scene, params, band, planes, planes_inout, nullptr, true, [&](const DAovFilm &F, float *) { return do_render_aov_adaptive(scene, camera, params, runs, planes, F, nullptr, stats); });
     });
 }
 

@@ -39,8 +39,8 @@ struct TileBackend : HostBackend {
 int render_tiles(TwinScene *s, const PtrsCamera *cam, const PtrsRenderParams *prm, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                  PtrsFilmPixel *film, PtrsFilmPixel *film_half, float *sample_rgb, PtrsStats *stats) {
     const uint32_t n_tiles = (uint32_t)(ad_tiles_x(prm->width) * ad_tiles_y(prm->height));
-    std::vector<uint8_t> flags(n_tiles); std::vector<uint32_t> list;
-    for (uint32_t t = 0; t < n_tiles; ++t) { flags[t] = tile_active[t] ? 1 : 0; if (flags[t]) list.push_back(t); }
+    std::vector<uint8_t> flags; std::vector<uint32_t> list;
+    ad_tile_list(tile_active, n_tiles, flags, list);
     if (list.empty()) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
     TileBackend be;
     be.stack_cap = (int)std::min<uint32_t>(s->H.stack_bound, 128u);
@@ -75,38 +75,32 @@ int adaptive_twin_render_tiles(void *sp, const PtrsCamera *cam, const PtrsRender
     return render_tiles(static_cast<TwinScene *>(sp), cam, prm, sample_begin, sample_end, tile_active, film, film_half, sample_rgb, stats);
 }
 
-// ptrs_render_adaptive's loop over the twin's tile form: the schedule, the error behind every block, the freeze rule.  history3: per
-// check {spp, tiles that took part} as two uint32 and the largest tile error's bits as the third; tile_errors (may be null): the tile
-// records of every check, n_checks x n_tiles.
+// ptrs_render_adaptive's loop (ad_block_loop, the one the product runs) over the twin's tile form and the host form of the film's error.
+// history3: per check {spp, tiles that took part} as two uint32 and the largest tile error's bits as the third; tile_errors (may be
+// null): the tile records of every check, n_checks x n_tiles.
 int adaptive_twin_render_adaptive(void *sp, const PtrsCamera *cam, const PtrsRenderParams *prm, float target, uint32_t min_spp, PtrsFilmPixel *film, PtrsFilmPixel *half,
                                   uint32_t *tile_spp, uint32_t *history3, uint32_t *n_checks_out, uint32_t *converged_out, PtrsTileError *tile_errors, uint64_t *samples_out) {
     if (!g_tables.ok) { g_err = "tables not loaded"; return PTRS_ERR_INVALID; }
     if (!sp || !cam || !prm || !film || !half || !tile_spp || !history3 || !n_checks_out || !converged_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
     uint32_t blocks[3 * PTRS_CONVERGE_MAX_CHECKS], n_blocks = 0;
     if (const char *m = cv_schedule(total_spp(*prm), min_spp, blocks, &n_blocks)) { g_err = m; return PTRS_ERR_INVALID; }
-    TwinScene *s = static_cast<TwinScene *>(sp);
     const uint32_t n_tiles = (uint32_t)(ad_tiles_x(prm->width) * ad_tiles_y(prm->height));
-    std::vector<uint8_t> active(n_tiles, 1);
-    std::vector<PtrsTileError> rec(n_tiles);
-    for (uint32_t t = 0; t < n_tiles; ++t) tile_spp[t] = 0;
-    uint32_t n_active = n_tiles, n_checks = 0; uint64_t samples = 0;
-    for (uint32_t k = 0; k < n_blocks && n_active != 0; ++k) {
-        for (int h = 0; h < 2; ++h) {
-            PtrsStats st;
-            int rc = render_tiles(s, cam, prm, blocks[3 * k + h], blocks[3 * k + h + 1], active.data(), film, h == 0 ? half : nullptr, nullptr, &st);
-            if (rc != PTRS_OK) return rc;
-            samples += st.samples;
+    struct Hooks {
+        TwinScene *s; const PtrsCamera *cam; const PtrsRenderParams *prm; PtrsFilmPixel *film, *half; PtrsTileError *tile_errors; uint32_t n_tiles;
+        int render(uint32_t begin, uint32_t end, bool with_half, const uint8_t *active, PtrsStats &st) { return render_tiles(s, cam, prm, begin, end, active, film, with_half ? half : nullptr, nullptr, &st); }
+        int measure(PtrsFilmErrorSummary &sum, PtrsTileError *records, uint64_t &) {
+            cv_film_error_host(prm->width, prm->height, film, half, records, &sum);
+            if (tile_errors) { std::memcpy(tile_errors, records, (size_t)n_tiles * sizeof(PtrsTileError)); tile_errors += n_tiles; }
+            return PTRS_OK;
         }
-        for (uint32_t t = 0; t < n_tiles; ++t) if (active[t]) tile_spp[t] = blocks[3 * k + 2];
-        PtrsFilmErrorSummary sum;
-        cv_film_error_host(prm->width, prm->height, film, half, rec.data(), &sum);
-        if (tile_errors) std::memcpy(tile_errors + (size_t)n_checks * n_tiles, rec.data(), (size_t)n_tiles * sizeof(PtrsTileError));
-        history3[3 * n_checks] = blocks[3 * k + 2]; history3[3 * n_checks + 1] = n_active; std::memcpy(&history3[3 * n_checks + 2], &sum.max_tile_error, 4);
-        ++n_checks;
-        n_active = ad_freeze(rec.data(), n_tiles, target, active.data(), active.data());
-    }
-    *n_checks_out = n_checks; *converged_out = n_active == 0u ? 1u : 0u;
-    if (samples_out) *samples_out = samples;
+    } hooks{static_cast<TwinScene *>(sp), cam, prm, film, half, tile_errors, n_tiles};
+    PtrsAdaptiveResult res; PtrsStats total; std::vector<uint32_t> spp_of;
+    int rc = ad_block_loop(blocks, n_blocks, n_tiles, target, true, hooks, res, spp_of, total);
+    if (rc != PTRS_OK) return rc;
+    std::memcpy(tile_spp, spp_of.data(), (size_t)n_tiles * 4);
+    for (uint32_t i = 0; i < res.n_checks; ++i) { history3[3 * i] = res.history[i].spp; history3[3 * i + 1] = res.history[i].tiles_active; std::memcpy(&history3[3 * i + 2], &res.history[i].max_tile_error, 4); }
+    *n_checks_out = res.n_checks; *converged_out = res.converged;
+    if (samples_out) *samples_out = total.samples;
     return PTRS_OK;
 }
 

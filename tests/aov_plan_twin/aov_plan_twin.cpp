@@ -105,9 +105,7 @@ int render_aov(TwinScene *s, const PtrsCamera *cam, const PtrsRenderParams *prm,
     job.sample_range = range;
     std::vector<uint8_t> flags; std::vector<uint32_t> list;
     if (tile_active) {
-        const uint32_t n_tiles = (uint32_t)(ad_tiles_x(prm->width) * ad_tiles_y(prm->height));
-        flags.resize(n_tiles);
-        for (uint32_t t = 0; t < n_tiles; ++t) { flags[t] = tile_active[t] ? 1 : 0; if (flags[t]) list.push_back(t); }
+        ad_tile_list(tile_active, (size_t)(ad_tiles_x(prm->width) * ad_tiles_y(prm->height)), flags, list);
         if (list.empty()) { if (stats) std::memset(stats, 0, sizeof(*stats)); return PTRS_OK; }
         job.tile_active = flags.data(); job.tile_active_host = flags.data(); job.tile_list = list.data(); job.n_tile_list = (uint32_t)list.size();
     }
