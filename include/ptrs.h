@@ -147,6 +147,17 @@ typedef struct PtrsCamera {
     float dy_camera[3];
 } PtrsCamera;
 
+/* Thin-lens camera (no counterpart in the reference, whose CameraSample holds p_film alone, sampler/mod.rs:162-166; DESIGN.md
+ * section 15): a PtrsCamera followed by the lens.  With PTRS_FLAG_THIN_LENS in params->flags every entry point that takes
+ * (camera, params) reads its `camera` argument as a PtrsCameraLens.  The lens is per call: no scene state, no option.
+ * A negative or non-finite lens_radius, or with lens_radius > 0 a focal_distance that is not finite and > 0, is refused
+ * (PTRS_ERR_INVALID) before the first device call.  lens_radius == 0 is the pinhole render bit for bit: no lens sample is drawn. */
+typedef struct PtrsCameraLens {
+    PtrsCamera camera;
+    float lens_radius;    /* >= 0, finite; 0 = pinhole */
+    float focal_distance; /* distance of the plane in focus from the lens plane along the view axis; finite, > 0 when lens_radius > 0 */
+} PtrsCameraLens;
+
 /* ---- render parameters (sampler/sobol.rs:35-60; integrator.rs:219-246) --------------------- */
 typedef struct PtrsRenderParams {
     int32_t width, height; /* film resolution (film.rs:132) */
@@ -172,7 +183,10 @@ enum { PTRS_SAMPLER_SOBOL = 0, PTRS_SAMPLER_STRATIFIED = 1 };
 enum {
     PTRS_FLAG_COUNTERS = 1u, /* fill nodes_visited / tris_tested (slower: device atomics) */
     PTRS_FLAG_TIMING = 2u,   /* hipEvent timing of every kernel launch (needs stream syncs) */
-    PTRS_FLAG_FILM_ZERO = 4u /* ptrs_render_multi: film_inout is all zeros (Film::clear), the devices clear their bands instead of uploading them */
+    PTRS_FLAG_FILM_ZERO = 4u, /* ptrs_render_multi: film_inout is all zeros (Film::clear), the devices clear their bands instead of uploading them */
+    PTRS_FLAG_THIN_LENS = 8u  /* `camera` points to a PtrsCameraLens.  Sobol': the lens sample is the get_2d behind the film sample (dimensions 2, 3) and the
+                                 path's dimension counter starts two higher; stratified: it is the pixel table's second 2-D dimension and the
+                                 n_sampled_dimensions requirement rises by one */
 };
 
 /* film pixel: linear RGB sums and filter-weight sum (film.rs:113-119; splat_xyz is never
@@ -529,6 +543,11 @@ typedef struct PtrsHit {
 } PtrsHit;
 int ptrs_trace_rays(PtrsScene *scene, uint32_t n, const float *rays, int32_t any_hit,
                     PtrsHit *hits_out, PtrsStats *stats);
+
+/* Autofocus for a PtrsCameraLens: the pinhole ray of raster point (raster_x, raster_y) is traced with ptrs_trace_rays' closest-hit
+ * kernel; *out = t * (-dir_cam.z), dir_cam the normalised camera-space direction: the depth of the hit along the view axis, which is
+ * what focal_distance measures.  A miss writes +inf and still returns PTRS_OK. */
+int ptrs_camera_focus_distance(PtrsScene *scene, const PtrsCamera *camera, float raster_x, float raster_y, float *out);
 
 /* Traversal bench (the reference's precedent: benches/benchmark_pathtracer.rs:35-54, scene.intersect on one ray in a loop).
  * ptrs_render_dump_rays: starts `params`' render, stops in its first pass before round `round` and returns that round's extension

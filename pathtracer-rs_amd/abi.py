@@ -12,7 +12,7 @@ TEX_CONSTANT, TEX_CHECKER, TEX_IMAGE = 0, 1, 2
 WRAP_REPEAT, WRAP_BLACK, WRAP_CLAMP = 0, 1, 2
 MAT_MATTE, MAT_METAL, MAT_MIRROR, MAT_GLASS, MAT_DISNEY, MAT_SUBSTRATE, MAT_NORMAL = range(7)
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_AREA, LIGHT_INFINITE = range(4)
-FLAG_COUNTERS, FLAG_TIMING, FLAG_FILM_ZERO = 1, 2, 4
+FLAG_COUNTERS, FLAG_TIMING, FLAG_FILM_ZERO, FLAG_THIN_LENS = 1, 2, 4, 8
 SAMPLER_SOBOL, SAMPLER_STRATIFIED = 0, 1
 # ptrs_render_aov: plane k = bit k; floats per sample of its per-sample export
 PtrsAovAlbedo, PtrsAovNormal, PtrsAovDepth = 1, 2, 4
@@ -76,6 +76,10 @@ class PtrsSceneDesc(C.Structure):
 class PtrsCamera(C.Structure):
     _fields_ = [("rot", C.c_float * 4), ("trans", C.c_float * 3), ("m00", C.c_float), ("m11", C.c_float), ("m22", C.c_float),
                 ("m23", C.c_float), ("raster_to_screen", C.c_float * 16), ("dx_camera", C.c_float * 3), ("dy_camera", C.c_float * 3)]
+
+
+class PtrsCameraLens(C.Structure):  # FLAG_THIN_LENS: what `camera` points to
+    _fields_ = [("camera", PtrsCamera), ("lens_radius", C.c_float), ("focal_distance", C.c_float)]
 
 
 class PtrsRenderParams(C.Structure):

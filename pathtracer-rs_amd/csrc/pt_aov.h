@@ -37,13 +37,15 @@ PT_HD int aov_albedo_slot(int32_t kind) {
 }
 
 // The planes' values of one camera sample: p_film and the hit word of round 0 (P.hit: packed triangle id, barycentrics).
+// `ray`: under a thin lens (C.lens_radius > 0) the ray generate_item made, origin and direction (its bits, read back from round 0's queue);
+// without a lens it is not read, the pinhole ray is a function of p_film.
 template <int FEAT>
-PT_HD AovRec aov_item(const DParams &R, const DCamera &C, const DScene &sc, f2 pf, u4 hit) {
+PT_HD AovRec aov_item(const DParams &R, const DCamera &C, const DScene &sc, f2 pf, u4 hit, const f3 *ray = nullptr) {
     AovRec a;
     a.albedo = a.normal = a.p = splat3(0.0f); a.coverage = 0.0f; a.depth = 0.0f; a.prim = 0xffffffffu;
     const int32_t prim = hit_prim(hit.x);
     if (prim < 0) return a;
-    const CamRay cr = camera_ray(C, pf, R.inv_sqrt_spp);
+    const CamRay cr = (ray && C.lens_radius > 0.0f) ? first_vertex_ray(C, pf, R.inv_sqrt_spp, ray[0], ray[1]) : camera_ray(C, pf, R.inv_sqrt_spp);
     const TriRegs T = load_tri_regs(sc.shade + prim);
     Surface s = tri_surface(T, prim, u2f(hit.y), u2f(hit.z), u2f(hit.w), -cr.d);
     surface_differentials(s, cr.o, cr.rx_d, cr.o, cr.ry_d);

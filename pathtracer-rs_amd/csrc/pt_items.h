@@ -22,13 +22,18 @@ namespace pt {
 
 struct CamRay { f3 o, d, rx_d, ry_d; };
 
-// Camera::generate_ray_differential (pathtracer/mod.rs:59-81) followed by
-// scale_differentials(1/sqrt(spp)) (ray.rs:30-35).  rx_origin == ry_origin == o.
-PT_HD CamRay camera_ray(const DCamera &C, f2 pf, float diff_scale) {
+// p_camera of a raster point: raster_to_screen (an Affine3 on (x, y, 0)), then Perspective3::unproject_point -- the one copy that
+// camera_ray and the lens ray's camera_dir share
+PT_HD f3 camera_point(const DCamera &C, f2 pf) {
     const float *m = C.r2s;
     f3 s = mk3(m[0] * pf.x + m[1] * pf.y + m[2] * 0.0f + m[3], m[4] * pf.x + m[5] * pf.y + m[6] * 0.0f + m[7], m[8] * pf.x + m[9] * pf.y + m[10] * 0.0f + m[11]);
     float inv_denom = C.m23 / (s.z + C.m22); // Perspective3::unproject_point
-    f3 pc = mk3(s.x * inv_denom / C.m00, s.y * inv_denom / C.m11, -inv_denom);
+    return mk3(s.x * inv_denom / C.m00, s.y * inv_denom / C.m11, -inv_denom);
+}
+// Camera::generate_ray_differential (pathtracer/mod.rs:59-81) followed by
+// scale_differentials(1/sqrt(spp)) (ray.rs:30-35).  rx_origin == ry_origin == o.
+PT_HD CamRay camera_ray(const DCamera &C, f2 pf, float diff_scale) {
+    f3 pc = camera_point(C, pf);
     CamRay r;
     r.o = quat_rotate(C.rot, splat3(0.0f)) + ld3(C.trans);
     f3 wd = quat_rotate(C.rot, pc);
@@ -38,6 +43,29 @@ PT_HD CamRay camera_ray(const DCamera &C, f2 pf, float diff_scale) {
     r.rx_d = r.d + (rxd - r.d) * diff_scale;
     r.ry_d = r.d + (ryd - r.d) * diff_scale;
     return r;
+}
+
+// The thin-lens ray (PtrsCameraLens; no counterpart in the reference): the pinhole ray's direction carried to the
+// plane in focus, seen from the point u_lens picks on the lens disk.  binary32, source order, like camera_ray.  The differentials are the
+// pinhole's scaled offsets carried onto the lens ray (first order in lens_radius / focal_distance: a definition of ours); origins = o.
+PT_HD CamRay lens_differentials(const CamRay &pin, f3 o, f3 d) { CamRay r; r.o = o; r.d = d; r.rx_d = d + (pin.rx_d - pin.d); r.ry_d = d + (pin.ry_d - pin.d); return r; }
+// the normalised camera-space direction of camera_ray's point
+PT_HD f3 camera_dir(const DCamera &C, f2 pf) { return normalize(camera_point(C, pf)); }
+PT_HD CamRay lens_ray(const DCamera &C, f2 pf, f2 u_lens, float diff_scale) {
+    const CamRay pin = camera_ray(C, pf, diff_scale);
+    f3 dir = camera_dir(C, pf);
+    f2 pl = concentric_disk(u_lens);
+    float ft = C.focal_distance / (-dir.z);
+    f3 oc = mk3(pl.x * C.lens_radius, pl.y * C.lens_radius, 0.0f);
+    f3 o = quat_rotate(C.rot, oc) + ld3(C.trans);
+    f3 d = normalize(quat_rotate(C.rot, dir * ft - oc));
+    return lens_differentials(pin, o, d);
+}
+// the camera differentials at a path's first vertex, from the ray generate_item made (ro, rd: its bits) and the path's p_film
+PT_HD CamRay first_vertex_ray(const DCamera &C, f2 pf, float diff_scale, f3 ro, f3 rd) {
+    const CamRay pin = camera_ray(C, pf, diff_scale);
+    if (C.lens_radius > 0.0f) return lens_differentials(pin, ro, rd);
+    return pin;
 }
 
 struct PathCoord { int32_t sx, sy, px, py; uint32_t s; };
@@ -57,21 +85,24 @@ PT_HD uint32_t strat_pack(uint32_t d1, uint32_t d2) { return (d1 & 63u) | ((d2 &
 
 PT_HD void generate_item(const DParams &R, const DSampler &S, const DCamera &C, const DPaths &P, uint32_t pid, uint32_t e) { // e: the path's position in round 0's extension queue
     PathCoord c = path_coord(R, S, pid);
-    f2 u; u4 st;
+    f2 u, ul = mk2(0.5f, 0.5f); u4 st;
+    const bool lens = C.lens_radius > 0.0f; // wave-uniform; a lens of radius 0 draws nothing: the pinhole render bit for bit
     if (S.kind == PTRS_SAMPLER_STRATIFIED) { // get_camera_sample = the first 2-D dimension of the pixel's table (mod.rs:156-160)
         const uint32_t pixel = (uint32_t)c.sy * (uint32_t)R.NX + (uint32_t)c.sx;
         const float *t = S.strat2 + (((size_t)pixel * S.strat_dims + 0u) * S.spp + c.s) * 2u;
         u = mk2(t[0], t[1]);
         st.x = pixel; st.y = c.s; st.z = strat_pack(0u, 1u) | ST_HAS_DIFF; st.w = 0;
+        if (lens) { ul = mk2(t[(size_t)S.spp * 2u], t[(size_t)S.spp * 2u + 1u]); st.z = strat_pack(0u, 2u) | ST_HAS_DIFF; } // the lens sample: the table's second 2-D dimension
     } else {
         SamplerState ss;
         ss.index = sobol_index(S, (uint64_t)c.s, (uint32_t)c.sx, (uint32_t)c.sy);
         ss.dim = 0; ss.scramble = pixel_scramble(c.px, c.py); ss.px = c.px; ss.py = c.py;
         u = get_2d(S, ss);
+        if (lens) ul = get_2d(S, ss); // the lens sample: the get_2d directly behind the film sample (dimensions 2 and 3); the path's counter starts two higher
         st.x = (uint32_t)ss.index; st.y = (uint32_t)(ss.index >> 32); st.z = ss.dim | ST_HAS_DIFF; st.w = ss.scramble; // the pixel's scramble travels with the path
     }
     f2 pf = mk2((float)c.px + u.x, (float)c.py + u.y);
-    CamRay r = camera_ray(C, pf, R.inv_sqrt_spp);
+    CamRay r = lens ? lens_ray(C, pf, ul, R.inv_sqrt_spp) : camera_ray(C, pf, R.inv_sqrt_spp);
     pslot(P.ray_o[0], e) = mkv4(r.o, PT_INF);
     pslot(P.ray_d[0], e) = mkv4(r.d, u2f(st.z)); // the path's state word (dimension counter | flags | bounces) travels with the ray direction: a vertex
                                           // that continues rewrites ray_d anyway, and `st` keeps only what never changes (Sobol' index, scramble)
@@ -267,7 +298,7 @@ PT_HD ShadeResult shade_item(const DParams &R, const DSampler &S, const DCamera 
     // (texture.rs:185-191, 430-445), so without image textures they are dead values.
     if ((FEAT & FEAT_IMAGE) && (stv.z & ST_HAS_DIFF)) {
         const f2a pf = pslot(P.pfilm, pid);
-        CamRay cr = camera_ray(C, mk2(pf.x, pf.y), R.inv_sqrt_spp);
+        CamRay cr = first_vertex_ray(C, mk2(pf.x, pf.y), R.inv_sqrt_spp, ro, rd); // (under a lens: the pinhole's offsets on the generated ray)
         surface_differentials(s, ro, cr.rx_d, ro, cr.ry_d);
     }
     // Everything this vertex writes is collected in `out` and stored by the caller (store_shade_out), behind X.before_stores(): the

@@ -178,8 +178,22 @@ struct RenderJob {
 template <class BE, class = void> struct has_tile_hooks : std::false_type {};
 template <class BE> struct has_tile_hooks<BE, std::void_t<decltype(std::declval<BE &>().generate_tiles((const uint8_t *)nullptr, (int32_t)0))>> : std::true_type {};
 
-inline DCamera make_camera(const PtrsCamera &cam) {
+// PtrsCameraLens' refusals; null: the lens is good
+inline const char *lens_error(float lens_radius, float focal_distance) {
+    if (!(lens_radius >= 0.0f && lens_radius < PT_INF)) return "thin lens: lens_radius must be finite and >= 0";
+    if (lens_radius > 0.0f && !(focal_distance > 0.0f && focal_distance < PT_INF)) return "thin lens: focal_distance must be finite and > 0";
+    return nullptr;
+}
+inline const char *lens_error(const PtrsCamera *cam, const PtrsRenderParams *prm) {
+    if (!cam || !prm || !(prm->flags & PTRS_FLAG_THIN_LENS)) return nullptr;
+    const PtrsCameraLens *L = reinterpret_cast<const PtrsCameraLens *>(cam);
+    return lens_error(L->lens_radius, L->focal_distance);
+}
+
+inline DCamera make_camera(const PtrsCamera &cam, uint32_t flags = 0u) { // flags: the render's; with PTRS_FLAG_THIN_LENS `cam` is the head of a PtrsCameraLens
     DCamera C;
+    C.lens_radius = 0.0f; C.focal_distance = 0.0f;
+    if (flags & PTRS_FLAG_THIN_LENS) { const PtrsCameraLens &L = reinterpret_cast<const PtrsCameraLens &>(cam); C.lens_radius = L.lens_radius; C.focal_distance = L.lens_radius > 0.0f ? L.focal_distance : 0.0f; }
     std::memcpy(C.rot, cam.rot, 16); std::memcpy(C.trans, cam.trans, 12);
     C.m00 = cam.m00; C.m11 = cam.m11; C.m22 = cam.m22; C.m23 = cam.m23;
     std::memcpy(C.r2s, cam.raster_to_screen, 64); std::memcpy(C.dxc, cam.dx_camera, 12); std::memcpy(C.dyc, cam.dy_camera, 12);
@@ -208,6 +222,8 @@ struct RenderSetup {
 template <class BE>
 int render_setup(BE &be, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRenderParams &prm, const RenderJob &job, RenderSetup &u, std::string &err) {
     if (prm.width <= 0 || prm.height <= 0 || prm.spp <= 0 || prm.max_depth < 0) { err = "bad render parameters"; return PTRS_ERR_INVALID; }
+    if (const char *m = lens_error(&cam, &prm)) { err = m; return PTRS_ERR_INVALID; }
+    const bool lens = (prm.flags & PTRS_FLAG_THIN_LENS) && reinterpret_cast<const PtrsCameraLens &>(cam).lens_radius > 0.0f;
     if (bvh_depth > 64) { err = "BVH deeper than the 64-entry traversal stack (accelerator.rs:370)"; return PTRS_ERR_UNSUPPORTED; }
     u = RenderSetup{};
     SampleGrid &g = u.g;
@@ -216,8 +232,8 @@ int render_setup(BE &be, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRe
         uint32_t &strat_dim = u.strat_dim;
         strat_dim = 1; while ((strat_dim + 1u) * (strat_dim + 1u) <= (uint32_t)prm.spp) ++strat_dim;
         if (strat_dim * strat_dim != (uint32_t)prm.spp) { err = "stratified sampler: spp must be dim_pixel_samples squared"; return PTRS_ERR_INVALID; }
-        if (prm.n_sampled_dimensions < 3 * (prm.max_depth + 1) + 1 || prm.n_sampled_dimensions > 63) {
-            err = "stratified sampler: n_sampled_dimensions must cover the path (3 * (max_depth + 1) + 1 .. 63): draws past it come from the tile's generator in path order (sampler/mod.rs:137-151), which a wavefront cannot reproduce";
+        if (prm.n_sampled_dimensions < 3 * (prm.max_depth + 1) + 1 + (lens ? 1 : 0) || prm.n_sampled_dimensions > 63) { // (a lens draws the table's second 2-D dimension)
+            err = "stratified sampler: n_sampled_dimensions must cover the path (3 * (max_depth + 1) + 1 .. 63, one more under a thin lens): draws past it come from the tile's generator in path order (sampler/mod.rs:137-151), which a wavefront cannot reproduce";
             return PTRS_ERR_UNSUPPORTED;
         }
         if (job.single_pixel) { err = "render_single_pixel with the stratified sampler is not supported (its tables depend on the tile's earlier pixels)"; return PTRS_ERR_UNSUPPORTED; }
@@ -249,7 +265,7 @@ int render_setup(BE &be, uint32_t bvh_depth, const PtrsCamera &cam, const PtrsRe
         int rc_t = be.strat_tables(g.NX, g.NY, u.strat_dim, S.strat_dims, &S.strat1, &S.strat2, err);
         if (rc_t != PTRS_OK) return rc_t;
     }
-    u.C = make_camera(cam);
+    u.C = make_camera(cam, prm.flags);
     DParams &R = u.R;
     R.max_depth = prm.max_depth; R.rr_threshold = prm.rr_threshold; R.rr_start_depth = prm.rr_start_depth; R.rr_enable = prm.rr_enable;
     R.NX = g.NX; R.NY = g.NY; R.W = prm.width; R.H = prm.height;

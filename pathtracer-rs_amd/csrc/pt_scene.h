@@ -157,11 +157,12 @@ struct DSampler { // SobolSamplerBuilder::new (sobol.rs:35-60) + table rows
     const float *strat2;        // [NX*NY][strat_dims][spp][2]
 };
 
-struct DCamera { // = PtrsCamera
+struct DCamera { // = PtrsCamera, then PtrsCameraLens' lens (0, 0 without PTRS_FLAG_THIN_LENS: the pinhole)
     float rot[4], trans[3];
     float m00, m11, m22, m23;
     float r2s[16];
     float dxc[3], dyc[3];
+    float lens_radius, focal_distance;
 };
 
 struct DParams {

@@ -1284,7 +1284,9 @@ __global__ __launch_bounds__(BLOCK) void k_aov(DParams R, DCamera C, DScene sc, 
         const uint32_t pid = pslot(Q.ext[0], e);
         const u4 r = pslot(P.hit, e);
         const f2a pf = pslot(P.pfilm, pid);
-        const AovRec a = aov_item<FEAT>(R, C, sc, mk2(pf.x, pf.y), r);
+        f3 ray[2] = {splat3(0.0f), splat3(0.0f)};
+        if (C.lens_radius > 0.0f) { ray[0] = xyz(pslot(P.ray_o[0], e)); ray[1] = xyz(pslot(P.ray_d[0], e)); } // (wave-uniform) the lens ray as generate_item left it
+        const AovRec a = aov_item<FEAT>(R, C, sc, mk2(pf.x, pf.y), r, ray);
         const uint32_t q = off + pid;
         pslot(A.albedo, q) = mkv4(a.albedo, a.coverage);
         pslot(A.normal, q) = mkv4(a.normal, a.depth);
@@ -1385,6 +1387,12 @@ struct DevBuf {
 };
 
 // ---- what every entry point asks first --------------------------------------------------------------
+// PtrsCameraLens: a bad lens is refused by every entry point that takes (camera, params), before anything else is looked at
+bool lens_refused(const PtrsCamera *camera, const PtrsRenderParams *params) {
+    const char *m = lens_error(camera, params);
+    if (m) g_err = m;
+    return m != nullptr;
+}
 int require_device(int *n_out = nullptr) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (this library has no CPU fallback)"; return PTRS_ERR_DEVICE; }
@@ -1561,7 +1569,7 @@ int require_spill(const PtrsScene *ps) {
 
 struct HipBackend {
     PtrsScene *ps; hipStream_t stream; SobolDevice *sob;
-    DScene sc; DSampler S; DCamera C; DParams R; DPaths P; DQueues Q;
+    DScene sc; DSampler S; DCamera C{}; DParams R; DPaths P; DQueues Q;
     uint32_t cap = 0, rows = 0, depth = 0, flags = 0, kinds_mask = 0;
     int feat = FEAT_FULL, feat_trace = FEAT_FULL;
     // Which traversal form this scene runs -- the template arguments of its kernels -- worked out ONCE (traversal_policy) and read by every
@@ -1846,11 +1854,12 @@ struct HipBackend {
     }
     // The Sobol' dimensions a vertex of round `it` can draw: a path starts the round at dimension <= 3 + 8 it (two camera
     // dimensions, the skipped dimension 4, at most 8 per vertex before) and draws at most 9 further ones; the window staged
-    // into LDS is the top of that range (paths below it -- long specular chains -- read the global tables).
+    // into LDS is the top of that range (paths below it -- long specular chains -- read the global tables).  Under a thin lens the
+    // camera draws two more dimensions (the lens sample, 2 and 3), so every path starts two higher and the window moves up by 2.
     ShadeLdsCfg shade_cfg(uint32_t it) const {
         ShadeLdsCfg c;
         c.sob_nib = (2u * S.log2_res + (31u - (uint32_t)__builtin_clz(S.spp)) <= 32u) ? 8u : (uint32_t)SOBOL_NIBBLES;
-        const uint32_t cap = SH_SOB_WORDS / sob_stride(c.sob_nib), top = std::min<uint32_t>(1024u, 3u + 8u * it + 9u);
+        const uint32_t cap = SH_SOB_WORDS / sob_stride(c.sob_nib), top = std::min<uint32_t>(1024u, 3u + 8u * it + 9u + (C.lens_radius > 0.0f ? 2u : 0u));
         c.sob_lo = top > cap ? top - cap : 0u; c.sob_n = top - c.sob_lo;
         c.tri_lds = (sc.n_prims * SH_TRI_REC_V4 <= SH_TRI_V4 && opt.shade_lds) ? 1u : 0u;
         c.n_lights_lds = opt.shade_lds ? std::min<uint32_t>(sc.n_lights, SH_LIGHTS) : 0u;
@@ -2456,7 +2465,7 @@ int ptrs_abi_sizeof(int which) {
         case 6: return (int)sizeof(PtrsCamera); case 7: return (int)sizeof(PtrsRenderParams); case 8: return (int)sizeof(PtrsStats);
         case 9: return (int)sizeof(PtrsHit); case 10: return (int)sizeof(PtrsFilmPixel); case 11: return (int)sizeof(PtrsDenoiseParams);
         case 12: return (int)sizeof(PtrsTileError); case 13: return (int)sizeof(PtrsFilmErrorSummary); case 14: return (int)sizeof(PtrsConvergeResult);
-        case 15: return (int)sizeof(PtrsAdaptiveCheck); case 16: return (int)sizeof(PtrsAdaptiveResult);
+        case 15: return (int)sizeof(PtrsAdaptiveCheck); case 16: return (int)sizeof(PtrsAdaptiveResult); case 17: return (int)sizeof(PtrsCameraLens);
         default: return -1;
     }
 }
@@ -2534,6 +2543,7 @@ int ptrs_scene_info(PtrsScene *scene, uint64_t *n_nodes, uint64_t *max_depth, ui
 }
 
 int ptrs_render_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, void *film_inout_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() {
         HipJob job;
         job.film = (v4 *)film_inout_device; job.stream = (hipStream_t)hip_stream; job.stats = stats;
@@ -2575,11 +2585,13 @@ static int render_samples_impl(PtrsScene *scene, const PtrsCamera *camera, const
     return render_host_films(scene, camera, params, band, job, film_inout, nullptr, sample_rgb);
 }
 int ptrs_render_samples(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, float *sample_rgb, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() { return render_samples_impl(scene, camera, params, film_inout, sample_rgb, stats); });
 }
 
 int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES],
                            float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         Request q = plane_request(planes, (const void *const *)planes_inout_device);
         q.params = Request::LEFT_TO_SETUP;
@@ -2591,6 +2603,7 @@ int ptrs_render_aov_device(PtrsScene *scene, const PtrsCamera *camera, const Ptr
 
 int ptrs_render_aov(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES],
                     float *sample_aov, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         Request q = plane_request(planes, (const void *const *)planes_inout);
         q.params = Request::NO_DEPTH;
@@ -2653,6 +2666,7 @@ int ptrs_denoise(PtrsDenoiser *d, const PtrsDenoiseParams *p, const PtrsFilmPixe
 // ---- sample ranges, the film's error, render until converged ------------------------------------------------------
 int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
                              void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = film_request(film_inout_device, film_half_inout_device);
@@ -2667,6 +2681,7 @@ int ptrs_render_range_device(PtrsScene *scene, const PtrsCamera *camera, const P
 
 int ptrs_render_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end,
                       PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = film_request(film_inout, film_half_inout);
@@ -2719,6 +2734,7 @@ int ptrs_converge_schedule(uint32_t spp, uint32_t min_spp, uint32_t *blocks_out,
 
 int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
                           PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, PtrsConvergeResult *result_out, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         PtrsAdaptiveResult res; std::vector<uint32_t> tile_spp;
         int rc = render_blocks(scene, camera, params, target_error, min_spp, false, film_inout, film_half_out, result_out, res, tile_spp, stats);
@@ -2733,6 +2749,7 @@ int ptrs_render_converged(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
 // ---- adaptive sampling: a sample range on some tiles, render until every tile has converged ---------------------------
 int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                              void *film_inout_device, void *film_half_inout_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = film_request(film_inout_device, film_half_inout_device);
@@ -2749,6 +2766,7 @@ int ptrs_render_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const P
 
 int ptrs_render_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                       PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_inout, float *sample_rgb, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = film_request(film_inout, film_half_inout);
@@ -2772,6 +2790,7 @@ int ptrs_adaptive_freeze(const PtrsTileError *tiles, uint32_t n_tiles, float tar
 
 int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float target_error, uint32_t min_spp,
                          PtrsFilmPixel *film_inout, PtrsFilmPixel *film_half_out, uint32_t *tile_spp_out, PtrsAdaptiveResult *result_out, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         PtrsAdaptiveResult res; std::vector<uint32_t> tile_spp;
         int rc = render_blocks(scene, camera, params, target_error, min_spp, true, film_inout, film_half_out, result_out, res, tile_spp, stats);
@@ -2785,6 +2804,7 @@ int ptrs_render_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsR
 // ---- feature planes for sample ranges and tiles; the planes of an adaptive film ------------------------------------------
 int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
                                  void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = plane_request(planes, (const void *const *)planes_inout_device);
@@ -2799,6 +2819,7 @@ int ptrs_render_aov_range_device(PtrsScene *scene, const PtrsCamera *camera, con
 
 int ptrs_render_aov_range(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, uint32_t planes,
                           PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = plane_request(planes, (const void *const *)planes_inout);
@@ -2814,6 +2835,7 @@ int ptrs_render_aov_range(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
 
 int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                                  uint32_t planes, void *const planes_inout_device[PTRS_AOV_PLANES], float *sample_aov_device, void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = plane_request(planes, (const void *const *)planes_inout_device);
@@ -2830,6 +2852,7 @@ int ptrs_render_aov_tiles_device(PtrsScene *scene, const PtrsCamera *camera, con
 
 int ptrs_render_aov_tiles(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t sample_begin, uint32_t sample_end, const uint8_t *tile_active,
                           uint32_t planes, PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], float *sample_aov, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         const uint32_t range[2] = {sample_begin, sample_end};
         Request q = plane_request(planes, (const void *const *)planes_inout);
@@ -2847,6 +2870,7 @@ int ptrs_render_aov_tiles(PtrsScene *scene, const PtrsCamera *camera, const Ptrs
 
 int ptrs_render_aov_adaptive_device(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
                                     void *const planes_inout_device[PTRS_AOV_PLANES], void *hip_stream, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         Request q = plane_request(planes, (const void *const *)planes_inout_device);
         q.min_spp = &min_spp; q.tile_spp = tile_spp; q.whole_film = "render_tiles";
@@ -2859,6 +2883,7 @@ int ptrs_render_aov_adaptive_device(PtrsScene *scene, const PtrsCamera *camera, 
 
 int ptrs_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t min_spp, const uint32_t *tile_spp, uint32_t planes,
                              PtrsFilmPixel *const planes_inout[PTRS_AOV_PLANES], PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         Request q = plane_request(planes, (const void *const *)planes_inout);
         q.min_spp = &min_spp; q.tile_spp = tile_spp; q.whole_film = "render_tiles";
@@ -2872,10 +2897,12 @@ int ptrs_render_aov_adaptive(PtrsScene *scene, const PtrsCamera *camera, const P
 }
 
 int ptrs_render(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return ptrs_render_samples(scene, camera, params, film_inout, nullptr, stats);
 }
 
 int ptrs_render_progressive(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, PtrsFilmPixel *film_inout, PtrsProgressFn fn, void *user, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         if (!scene || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         HIPCHK(hipSetDevice(scene->device));
@@ -2900,6 +2927,7 @@ int ptrs_plan_bands(int32_t height, uint32_t n, const float *row_cost, int32_t *
 // milliseconds where the planner of round 3 made 64 strip renders (270 ms for Cornell).  row_cost_out[y], y in [0, height): the queries of
 // the sample row under output row y (grid row y + 2); the apron's rows are left out.
 int ptrs_render_row_cost(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, float *row_cost_out, PtrsStats *stats) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         if (!scene || !camera || !params || !row_cost_out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         if (params->width <= 0 || params->height <= 0) { g_err = "bad render parameters"; return PTRS_ERR_INVALID; }
@@ -2934,6 +2962,7 @@ int ptrs_scene_set_option(PtrsScene *scene, const char *name, int64_t value) {
 
 int ptrs_render_multi(PtrsScene *const *scenes, uint32_t n, const PtrsCamera *camera, const PtrsRenderParams *params, const int32_t *band_bounds,
                       PtrsFilmPixel *film_inout, PtrsStats *stats_per_scene) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         if (!scenes || n == 0 || !camera || !params || !film_inout) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         for (uint32_t i = 0; i < n; ++i) {
@@ -3021,6 +3050,7 @@ int ptrs_render_multi(PtrsScene *const *scenes, uint32_t n, const PtrsCamera *ca
 }
 
 int ptrs_render_single_pixel(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, int32_t px, int32_t py, float *rgb_out) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     // render_single_pixel (integrator.rs:505-534): the sampler is started on `pixel` and li() evaluated for each of its samples;
     // the reference accepts any pixel (it never touches the film), here: any pixel of the sample bounds, apron included.  Only
     // that pixel's spp paths are traced.
@@ -3094,7 +3124,26 @@ int ptrs_trace_rays(PtrsScene *scene, uint32_t n, const float *rays, int32_t any
     return guarded([&]() { return trace_rays_impl(scene, n, rays, any_hit, hits_out, stats); });
 }
 
+// Autofocus: the pinhole ray of a raster point through ptrs_trace_rays' closest-hit path; the hit's depth along the view axis is
+// t * (-dir_cam.z), dir_cam the normalised camera-space direction of camera_ray (a rotation keeps the length: world t = camera t).
+int ptrs_camera_focus_distance(PtrsScene *scene, const PtrsCamera *camera, float raster_x, float raster_y, float *out) {
+    return guarded([&]() -> int {
+        if (!scene || !camera || !out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
+        if (!(raster_x > -PT_INF && raster_x < PT_INF && raster_y > -PT_INF && raster_y < PT_INF)) { g_err = "focus_distance: the raster point must be finite"; return PTRS_ERR_INVALID; }
+        const DCamera C = make_camera(*camera);
+        const f2 pf = mk2(raster_x, raster_y);
+        const CamRay r = camera_ray(C, pf, 1.0f);
+        const float ray[7] = {r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, PT_INF};
+        PtrsHit h;
+        int rc = trace_rays_impl(scene, 1u, ray, 0, &h, nullptr);
+        if (rc != PTRS_OK) return rc;
+        *out = h.prim < 0 ? PT_INF : h.t * (-camera_dir(C, pf).z);
+        return PTRS_OK;
+    });
+}
+
 int ptrs_render_dump_rays(PtrsScene *scene, const PtrsCamera *camera, const PtrsRenderParams *params, uint32_t round, uint32_t max_rays, float *rays_out, uint32_t *n_out) {
+    if (lens_refused(camera, params)) return PTRS_ERR_INVALID;
     return guarded([&]() -> int {
         if (!scene || !camera || !params || !rays_out || !n_out || max_rays == 0) { g_err = "null argument"; return PTRS_ERR_INVALID; }
         HIPCHK(hipSetDevice(scene->device));
@@ -3320,10 +3369,10 @@ int ptrs_probe_shade_tables(PtrsScene *scene, const PtrsRenderParams *params, ui
         if (const char *why = probe_shade_rows_check(&scene->H, op, n, rows)) { g_err = why; return PTRS_ERR_INVALID; }
         return with_backend(scene, params, nullptr, [&](HipBackend &be, std::string &err) -> int {
             RenderSetup u;
-            const PtrsCamera cam{};
-            int rc = render_setup(be, scene->H.max_depth, cam, *params, RenderJob{}, u, err);
+            const PtrsCameraLens cam{}; // (the probe takes no camera: a pinhole's tables, whatever params->flags says)
+            int rc = render_setup(be, scene->H.max_depth, cam.camera, *params, RenderJob{}, u, err);
             if (rc != PTRS_OK) return rc;
-            be.sc = scene->sc; be.S = u.S; be.feat = scene_features(scene->H);
+            be.sc = scene->sc; be.S = u.S; be.C = u.C; be.feat = scene_features(scene->H);
             const ShadeLdsCfg cfg = be.shade_cfg(it);
             const uint32_t header[PROBE_SHADE_HEADER] = {cfg.sob_lo, cfg.sob_n, cfg.sob_nib, cfg.tri_lds, cfg.n_lights_lds, cfg.marg_li, cfg.pre_li, (uint32_t)be.feat, be.env_presampled_only() ? 1u : 0u, 0u, 0u, 0u};
             std::memcpy(header_out, header, sizeof(header));

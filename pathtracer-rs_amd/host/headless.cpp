@@ -7,6 +7,7 @@
 //   -> preprocess -> render -> save.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +32,8 @@ int main(int argc, char **argv) {
     double target_error = -1.0; int min_samples = 8; // --target_error: render until the film's error is below it, -s is then the ceiling
     int spp = 1, max_depth = 15, w = 640, h = 480; // DEFAULT_RESOLUTION common/mod.rs:14
     bool have_out = false;
+    bool have_aperture = false, have_focus = false, have_focus_at = false; // the thin lens (not in the reference): they override a thinlens sensor's values
+    float aperture = 0.0f, focus = 0.0f, focus_x = 0.0f, focus_y = 0.0f;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "error: %s needs a value\n", name); std::exit(2); } return argv[++i]; };
@@ -53,16 +56,28 @@ int main(int argc, char **argv) {
         else if (a == "--min_samples") min_samples = std::atoi(need("--min_samples"));     // largest tile error is below E (ptrs_render_converged); prints every check and the count it stopped at
         else if (a == "--adaptive") adaptive = true;                   // with --target_error: every block only on the 16 x 16 tiles still above E (ptrs_render_adaptive); writes samples.png next to render.png;
                                                                        // --aov / --denoise then take their planes from ptrs_render_aov_adaptive: every tile's planes hold the samples its film pixels hold
+        else if (a == "--aperture") { aperture = std::strtof(need("--aperture"), nullptr); have_aperture = true; }  // lens radius in scene units (0: pinhole)
+        else if (a == "--focus") { focus = std::strtof(need("--focus"), nullptr); have_focus = true; }             // depth of the plane in focus along the view axis
+        else if (a == "--focus_at") {                                                                               // autofocus: that depth from what raster point X,Y shows (ptrs_camera_focus_distance)
+            const char *v = need("--focus_at"); char *e;
+            focus_x = std::strtof(v, &e);
+            if (e == v || *e != ',') { std::fprintf(stderr, "error: --focus_at needs X,Y\n"); return 2; }
+            const char *v2 = e + 1;
+            focus_y = std::strtof(v2, &e);
+            if (e == v2 || *e != 0) { std::fprintf(stderr, "error: --focus_at needs X,Y\n"); return 2; }
+            have_focus_at = true;
+        }
         else if (a == "--headless") {}
         else if (a == "-c" || a == "--camera" || a == "-l" || a == "--log_level" || a == "-m" || a == "--module_log" || a == "--server") (void)need(a.c_str());
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "error: unknown flag %s\n", a.c_str()); return 2; }
         else scene_path = a;
     }
     if (scene_path.empty() || (!have_out && dump_path.empty() && dump_full_path.empty())) {
-        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--target_error E [--min_samples N] [--adaptive]] [--headless]\n");
+        std::fprintf(stderr, "usage: ptrs_headless SCENE(.xml|.gltf|.glb) -o DIR [-s SPP] [-r WxH] [-d DEPTH] [--default_lights --env_map FILE.hdr] [--gpus N [--even_bands]] [--preview] [--progress] [--aov] [--denoise] [--target_error E [--min_samples N] [--adaptive]] [--aperture R] [--focus D | --focus_at X,Y] [--headless]\n");
         return 2;
     }
     if (target_error >= 0.0 && (n_gpus > 1 || preview || progress)) { std::fprintf(stderr, "error: --target_error does not combine with --gpus, --preview or --progress\n"); return 2; }
+    if (have_focus && have_focus_at) { std::fprintf(stderr, "error: --focus and --focus_at exclude each other\n"); return 2; }
     if (adaptive && target_error < 0.0) { std::fprintf(stderr, "error: --adaptive needs --target_error\n"); return 2; }
     Camera camera; RenderScene scene; std::string err;
     if (!import_scene(scene_path, w, h, camera, scene, err, default_lights, env_map_path)) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
@@ -72,6 +87,16 @@ int main(int argc, char **argv) {
     camera.film.get_sample_bounds(sb);
     PathIntegrator integrator(SamplerBuilder(spp, sb), max_depth, progress || preview);
     integrator.preprocess(scene);
+    if (have_aperture || have_focus || have_focus_at) {
+        float r = have_aperture ? aperture : camera.lens.lens_radius, fd = have_focus ? focus : camera.lens.focal_distance;
+        if (have_focus_at) {
+            const int rc_f = integrator.focus_distance(camera, scene, focus_x, focus_y, fd);
+            if (rc_f != PTRS_OK) { std::fprintf(stderr, "error: autofocus failed (%d): %s\n", rc_f, integrator.last_error.c_str()); return 1; }
+            if (!(fd < HUGE_VALF)) { std::fprintf(stderr, "error: --focus_at %g,%g: the ray hits nothing to focus on\n", (double)focus_x, (double)focus_y); return 1; }
+            std::fprintf(stderr, "INFO focus distance %.6g\n", (double)fd);
+        }
+        if (!camera.set_lens(r, fd)) { std::fprintf(stderr, "error: bad lens: --aperture must be finite and >= 0, and with an aperture the focus distance (--focus, --focus_at or the scene's) finite and > 0\n"); return 2; }
+    }
     if (preview && have_out) integrator.on_pass = [&](uint32_t done, uint32_t total, int32_t, int32_t) {
         std::string e;
         if (done < total && !write_png_rgba8(out_dir + "/render.png", camera.film.width, camera.film.height, camera.film.to_rgba_image(), e)) std::fprintf(stderr, "\nwarning: preview: %s\n", e.c_str());

@@ -93,6 +93,7 @@ PtrsRenderParams PathIntegrator::params(const Camera &camera) const {
     p.width = camera.film.width; p.height = camera.film.height; p.spp = sb_.samples_per_pixel; p.max_depth = max_depth_;
     p.rr_threshold = rr_threshold_; p.rr_start_depth = rr_start_depth_; p.rr_enable = rr_enable_ ? 1 : 0;
     p.row_begin = 0; p.row_end = camera.film.height; p.device = device_; p.paths_per_pass = 0; p.flags = 0;
+    if (camera.lens.lens_radius > 0.0f) p.flags |= PTRS_FLAG_THIN_LENS; // &camera.abi is then read as the head of camera.lens
     return p;
 }
 int PathIntegrator::ensure_scene(RenderScene &scene) {
@@ -226,6 +227,19 @@ int PathIntegrator::render_aov_adaptive(Camera &camera, RenderScene &scene, uint
     if (rc != PTRS_OK) last_error = ptrs_last_error();
     return rc;
 }
+int PathIntegrator::focus_distance(Camera &camera, RenderScene &scene, float raster_x, float raster_y, float &out) {
+    int rc = ensure_scene(scene);
+    if (rc != PTRS_OK) return rc;
+    rc = ptrs_camera_focus_distance(gpu_scene_, &camera.abi, raster_x, raster_y, &out);
+    if (rc != PTRS_OK) last_error = ptrs_last_error();
+    return rc;
+}
+bool Camera::set_lens(float lens_radius, float focal_distance) {
+    if (!(lens_radius >= 0.0f && std::isfinite(lens_radius))) return false;
+    if (lens_radius > 0.0f && !(focal_distance > 0.0f && std::isfinite(focal_distance))) return false;
+    lens.lens_radius = lens_radius; lens.focal_distance = lens_radius > 0.0f ? focal_distance : 0.0f;
+    return true;
+}
 int PathIntegrator::render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats) {
     int rc = ensure_scene(scene);
     if (rc != PTRS_OK) return rc;
@@ -262,7 +276,7 @@ int PathIntegrator::render_multi(Camera &camera, RenderScene &scene, int n_devic
     int rc = PTRS_OK;
     if (cost_weighted && n_devices > 1) {
         // the plan of a view is made once: a second frame of the same scene, camera, resolution and depth on the same devices pays nothing
-        std::string key((const char *)&camera.abi, sizeof(camera.abi));
+        std::string key((const char *)&camera.lens, sizeof(camera.lens));
         key.append((const char *)&p.width, sizeof(p.width)).append((const char *)&p.height, sizeof(p.height)).append((const char *)&p.max_depth, sizeof(p.max_depth)).append((const char *)&n_devices, sizeof(n_devices));
         if (key != plan_key_) {
             if (!probe_row_cost(multi_scenes_[0], camera.abi, p, 0, cost, last_error)) return PTRS_ERR_DEVICE;
@@ -640,6 +654,12 @@ bool import_scene(const std::string &path, int res_w, int res_h, Camera &camera,
     auto cm = parse_floats(tf->child("matrix")->get("value"));
     if (cm.size() != 16) { err = "camera matrix needs 16 values"; return false; }
     make_camera(cm.data(), std::strtof(fovn->get("value").c_str(), nullptr), std::atoi(fw->get("value").c_str()), std::atoi(fh->get("value").c_str()), res_w, res_h, camera);
+    camera.set_lens(0.0f, 0.0f);
+    if (sensor->get("type") == "thinlens") { // Mitsuba's thin-lens sensor: aperture_radius, focus_distance
+        const Node *ap = sensor->child_named("float", "aperture_radius"), *fd = sensor->child_named("float", "focus_distance");
+        if (!ap || !fd) { err = "thinlens sensor: aperture_radius and focus_distance are required"; return false; }
+        if (!camera.set_lens(std::strtof(ap->get("value").c_str(), nullptr), std::strtof(fd->get("value").c_str(), nullptr))) { err = "thinlens sensor: aperture_radius must be finite and >= 0, focus_distance finite and > 0"; return false; }
+    }
     scene = RenderScene();
     const size_t slash = path.find_last_of('/');
     const std::string base = slash == std::string::npos ? "." : path.substr(0, slash);
@@ -729,6 +749,8 @@ bool write_png_rgba8(const std::string &path, int w, int h, const std::vector<ui
 }
 
 // ---- scene dump (for the cross-check against the Python host, tests/test_host_cpp.py) -------------------------
+// PTRSDUMP: magic, the PtrsCamera, meshes, materials, textures, lights, then a 12-byte trailer "LENS" + lens_radius + focal_distance
+// (readers of the earlier form stop before it).  PTRSDMP2, the full form, has no trailer: its reader holds it to the last byte.
 bool dump_scene(const std::string &path, const Camera &cam, const RenderScene &s) {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -746,6 +768,7 @@ bool dump_scene(const std::string &path, const Camera &cam, const RenderScene &s
     for (auto &t : s.textures) { w32((uint32_t)t.kind); w32((uint32_t)t.channels); std::fwrite(t.value, 4, 3, f); std::fwrite(t.value2, 4, 3, f); }
     w32((uint32_t)s.lights.size());
     for (auto &l : s.lights) { w32((uint32_t)l.kind); w32(l.mesh); w32(l.tri); w32((uint32_t)l.ke_tex); }
+    std::fwrite("LENS", 1, 4, f); std::fwrite(&cam.lens.lens_radius, 4, 1, f); std::fwrite(&cam.lens.focal_distance, 4, 1, f); // trailer: the thin lens
     std::fclose(f);
     return true;
 }

@@ -34,7 +34,14 @@ struct Film {
 };
 
 struct Camera {
-    PtrsCamera abi{};
+    // `abi` is the PtrsCamera the render calls take, as before; `lens` is the PtrsCameraLens whose head it is (the thin lens behind it:
+    // lens_radius 0 is the pinhole; not in the reference).  With a lens PathIntegrator::params sets PTRS_FLAG_THIN_LENS and the calls
+    // read on from &abi into `lens`: the two share their storage (a struct and its first member are at one address).
+    union {
+        PtrsCameraLens lens{};
+        PtrsCamera abi;
+    };
+    bool set_lens(float lens_radius, float focal_distance); // false: a bad lens (negative or non-finite radius; with a radius, a focal distance that is not finite and > 0)
     Film film;
 };
 
@@ -111,6 +118,8 @@ public:
     int render_aov_adaptive(Camera &camera, RenderScene &scene, uint32_t min_spp, const std::vector<uint32_t> &tile_spp, uint32_t planes, std::vector<PtrsFilmPixel> planes_inout[PTRS_AOV_PLANES], PtrsStats *stats = nullptr);
     // ptrs_render_tiles: samples [sample_begin, sample_end) on the active tiles (tiles_x * tiles_y flag bytes) into camera.film
     int render_tiles(Camera &camera, RenderScene &scene, uint32_t sample_begin, uint32_t sample_end, const std::vector<uint8_t> &tile_active, PtrsStats *stats = nullptr);
+    // ptrs_camera_focus_distance: the depth along the view axis of what the pinhole ray of a raster point hits (inf on a miss): the focal_distance that puts it in focus
+    int focus_distance(Camera &camera, RenderScene &scene, float raster_x, float raster_y, float &out);
     // another sample count for the renders that follow (the planes of render_aov at the count render_converged stopped at)
     void set_samples_per_pixel(int spp) { sb_ = SamplerBuilder(spp, sb_.sample_bounds); }
     // When set, render() publishes the film after every pass of the pipeline (ptrs_render_progressive) and calls this with
@@ -154,7 +163,7 @@ bool probe_row_cost(PtrsScene *scene, const PtrsCamera &camera, const PtrsRender
 
 // importer::import for Mitsuba XML (rectangle / cube / sphere / obj shapes, twosided / diffuse / conductor /
 // roughconductor / dielectric / plastic / roughplastic bsdfs with rgb or checkerboard / bitmap texture parameters,
-// area emitters on shapes, envmap / sunsky emitters, perspective sensor).  Returns false and fills err on failure.
+// area emitters on shapes, envmap / sunsky emitters, perspective and thinlens sensors).  Returns false and fills err on failure.
 // A sunsky emitter falls back to data/abandoned_tank_farm_04_1k.hdr, looked for next to the executable's directory
 // (../data) and under the working directory, unless env_map_path names another Radiance file.
 bool import_scene(const std::string &path, int res_w, int res_h, Camera &camera, RenderScene &scene, std::string &err,

@@ -209,6 +209,8 @@ class PathIntegrator:
         p.rr_threshold, p.rr_start_depth, p.rr_enable = self.rr_threshold, self.rr_start_depth, int(self.rr_enable)
         p.row_begin, p.row_end = row_begin, (row_end if row_end else camera.film.height)
         p.device, p.paths_per_pass, p.flags = self.device, self.paths_per_pass, flags
+        if getattr(camera, "lens_radius", 0.0) > 0.0:  # camera.to_abi() is then a PtrsCameraLens
+            p.flags |= abi.FLAG_THIN_LENS
         if isinstance(self.sampler_builder, StratifiedSamplerBuilder):
             p.sampler, p.n_sampled_dimensions = abi.SAMPLER_STRATIFIED, self.sampler_builder.n_sampled_dimensions
         return p
@@ -741,6 +743,18 @@ def trace_rays(scene, rays, any_hit=False, device=0, bvh=None):
     stats = abi.PtrsStats()
     _check(load_library().ptrs_trace_rays(ds.handle, rays.shape[0], C.c_void_p(rays.ctypes.data), int(any_hit), C.c_void_p(hits.ctypes.data), C.byref(stats)))
     return hits, stats
+
+
+def focus_distance(camera, scene, raster_xy, device=0):
+    """ptrs_camera_focus_distance: the depth along the view axis of what the pinhole ray of raster point `raster_xy` hits -- the
+    focal_distance that puts it in focus (Camera.with_lens); inf on a miss."""
+    ds = _device_scene(scene, device)
+    L = load_library()
+    L.ptrs_camera_focus_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    cam = camera.with_lens(0.0, 0.0).to_abi()
+    out = C.c_float(0.0)
+    _check(L.ptrs_camera_focus_distance(ds.handle, C.byref(cam), float(raster_xy[0]), float(raster_xy[1]), C.byref(out)))
+    return float(out.value)
 
 
 def dump_rays(integrator, camera, scene, round_no, max_rays):

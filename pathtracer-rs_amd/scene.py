@@ -14,6 +14,7 @@ emitters, the perspective sensor.  Everything here is host-side set-up that the
 reference also does once, outside PathIntegrator::render; the results cross the C ABI as flat
 arrays (include/ptrs.h).  All arithmetic is binary32 in the order nalgebra 0.32.2 performs it.
 """
+import copy
 import math
 import os
 import warnings
@@ -278,16 +279,38 @@ class Camera:
         self.dx_camera = px - p0
         self.dy_camera = py - p0
         self.film = Film(int(resolution[0]), int(resolution[1]))
+        # the thin lens (PtrsCameraLens; not in the reference): radius 0 is the pinhole
+        self.lens_radius, self.focal_distance = 0.0, 0.0
+
+    def with_lens(self, lens_radius, focal_distance):
+        """This camera with a thin lens of `lens_radius` focused on the plane at depth `focal_distance` along the view axis
+        (focus_distance() measures one), with a cleared film of its own.  Radius 0 gives the pinhole back."""
+        lens_radius, focal_distance = float(lens_radius), float(focal_distance)
+        if not (0.0 <= lens_radius < math.inf) or (lens_radius > 0.0 and not (0.0 < focal_distance < math.inf)):
+            raise ValueError("thin lens: lens_radius must be finite and >= 0, focal_distance finite and > 0")
+        c = copy.copy(self)
+        c.film = Film(self.film.width, self.film.height)
+        c.lens_radius, c.focal_distance = lens_radius, (focal_distance if lens_radius > 0.0 else 0.0)
+        return c
 
     def to_abi(self):
+        """The PtrsCamera; with a lens the PtrsCameraLens that PTRS_FLAG_THIN_LENS announces (PathIntegrator.params sets the flag)."""
+        if self.lens_radius > 0.0:
+            cl = abi.PtrsCameraLens()
+            self._fill_abi(cl.camera)
+            cl.lens_radius, cl.focal_distance = self.lens_radius, self.focal_distance
+            return cl
         c = abi.PtrsCamera()
+        self._fill_abi(c)
+        return c
+
+    def _fill_abi(self, c):
         c.rot[:] = [float(x) for x in self.rot]
         c.trans[:] = [float(x) for x in self.trans]
         c.m00, c.m11, c.m22, c.m23 = float(self.m00), float(self.m11), float(self.m22), float(self.m23)
         c.raster_to_screen[:] = [float(x) for x in self.raster_to_screen.reshape(16)]
         c.dx_camera[:] = [float(x) for x in self.dx_camera]
         c.dy_camera[:] = [float(x) for x in self.dy_camera]
-        return c
 
 
 def camera_from_matrix(cam_to_world4, fov_deg, film_w, film_h, resolution):
@@ -557,6 +580,11 @@ def import_scene(path, resolution, default_lights=False, env_map=None):
     fw = int(film.find("integer[@name='width']").get("value"))
     fh = int(film.find("integer[@name='height']").get("value"))
     cam = camera_from_matrix(_parse_matrix(sensor.find("transform/matrix")).reshape(16), fov, fw, fh, resolution)
+    if sensor.get("type") == "thinlens":  # Mitsuba's thin-lens sensor: aperture_radius, focus_distance
+        ap, fd = sensor.find("float[@name='aperture_radius']"), sensor.find("float[@name='focus_distance']")
+        if ap is None or fd is None:
+            raise ValueError("thinlens sensor: aperture_radius and focus_distance are required")
+        cam = cam.with_lens(float(ap.get("value")), float(fd.get("value")))
     scene = RenderScene()
     named = {}
     for b in root.findall("bsdf"):
