@@ -281,7 +281,27 @@ const char *ptrs_last_error(void);
 
 /* Uploads the scene and (unless desc->bvh_nodes is given) builds the accelerator on the host.
  * Replaces: RenderScene construction hand-off, the precedent being OptixAccelerator::new(&scene)
- * (src/pathtracer/gpu/optix.rs:160-290) which consumes the same flat mesh arrays. */
+ * (src/pathtracer/gpu/optix.rs:160-290) which consumes the same flat mesh arrays.
+ *
+ * The description is checked, and the host copy built, BEFORE the first device call: a description that breaks a rule below is refused
+ * with PTRS_ERR_INVALID (an unknown material or light kind: PTRS_ERR_UNSUPPORTED) and a message that names the rule, on a machine
+ * without a GPU too; a valid one gets PTRS_ERR_DEVICE there.  Nothing of a refused description reaches a device.
+ *  - A non-zero count comes with its array: meshes, materials, textures, lights; an IMAGE texture's level_data, level_cols, level_rows
+ *    and every level_data[l]; an INFINITE light's four tables; bvh_prims with bvh_nodes.
+ *  - Textures: kind 0..2, channels 1 or 3; IMAGE: n_levels >= 1, every level at least 1 x 1, wrap one of PTRS_WRAP_*.
+ *  - Materials: every tex[k] is -1 or a texture; the slots the kind names hold textures of the channel counts above (Metal: `roughness`,
+ *    or u_rough and v_rough together, all 1-channel); NORMAL: inner is another material, and a chain of wrappers reaches a material of
+ *    another kind within four steps (no wrapper of itself, no cycle), whether a mesh uses it or not.
+ *  - Meshes: material in range, alpha_mask_tex -1 or a 1-channel texture.  A mesh with n_tris == 0 is legal whatever its pointers and its
+ *    vertex count are: none is read, and it contributes nothing (later meshes keep their global triangle ids).  With triangles: pos and
+ *    indices present, every index < n_verts, every position finite -- a NaN or an infinity is refused, the message names mesh and vertex.
+ *  - A scene without any triangle (no mesh, or only empty ones) is legal: every ray misses, the lights that need no geometry still
+ *    shine.  ptrs_scene_info and PtrsStats::bvh_nodes then report the one traversal record no ray can enter: 1 node, 0 triangles.
+ *  - Lights: AREA names a triangle of a mesh and a 3-channel ke_tex; INFINITE a 3-channel IMAGE lmap_tex and dist_nu, dist_nv >= 1.
+ *  - A pre-built tree: a leaf's range [offset, offset + num_prims) lies within the triangles (tested in 64 bits); an interior node's
+ *    offset is a node, its first child i + 1 exists, its axis is 0..2; every bvh_prims entry is a triangle id; and walking from node 0,
+ *    every node is reached EXACTLY once (no node shared by two parents, none skipped, no cycle) at a depth of at most 4096.  The check
+ *    is linear in the description's size. */
 int ptrs_scene_create(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out);
 void ptrs_scene_destroy(PtrsScene *scene);
 /* accelerator facts (the reference logs these: accelerator.rs:131-148); any pointer may be NULL */

@@ -626,6 +626,8 @@ struct Scene {
         meshes.resize(d.n_meshes); mesh_first_tri.resize(d.n_meshes);
         for (uint32_t m = 0; m < d.n_meshes; m++) {
             const PtrsMesh &s = d.meshes[m]; Mesh &M = meshes[m];
+            mesh_first_tri[m] = (uint32_t)tris.size();
+            if (!s.n_tris) { M.material = s.material; M.alpha_mask = s.alpha_mask_tex; continue; } // a mesh without triangles is legal whatever its pointers are (include/ptrs.h): none is read
             M.pos.resize(s.n_verts);
             for (uint32_t v = 0; v < s.n_verts; v++) M.pos[v] = Vec3(s.pos[3 * v], s.pos[3 * v + 1], s.pos[3 * v + 2]);
             if (s.normal) { M.normal.resize(s.n_verts); for (uint32_t v = 0; v < s.n_verts; v++) M.normal[v] = Vec3(s.normal[3 * v], s.normal[3 * v + 1], s.normal[3 * v + 2]); }

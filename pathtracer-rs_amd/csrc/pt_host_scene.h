@@ -36,6 +36,9 @@ struct HostScene {
     uint32_t stack_bound = 0; // most entries the pair-node traversal can have stacked (= depth of the pair tree)
     bool kinds_present[7] = {false, false, false, false, false, false, false};
     bool has_alpha = false;
+    // the node count the library reports (ptrs_scene_info, PtrsStats::bvh_nodes): the binary tree's, or for a scene without a triangle the one
+    // traversal record no ray can enter (build_host_scene)
+    uint32_t reported_nodes() const { return nodes.empty() ? (uint32_t)(nodes2.size() + nodes4.size()) : (uint32_t)nodes.size(); }
 };
 
 namespace hostbvh {
@@ -127,22 +130,32 @@ struct Builder {
 // fetching too.  An order, not a different tree: same visits, same results.
 inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &err, int node_form = 0, int node_order = 0) {
     auto bad = [&](const char *m) { err = m; return (int)PTRS_ERR_INVALID; };
+    // a count without its array is refused before anything is read through it
     if (d.n_meshes && !d.meshes) return bad("meshes is NULL");
+    if (d.n_textures && !d.textures) return bad("textures is NULL");
+    if (d.n_materials && !d.materials) return bad("materials is NULL");
+    if (d.n_lights && !d.lights) return bad("lights is NULL");
     // ---- textures -------------------------------------------------------------------------------
     H.texs.resize(d.n_textures);
     for (uint32_t i = 0; i < d.n_textures; ++i) {
         const PtrsTexture &s = d.textures[i]; DTexture &t = H.texs[i];
         std::memset(&t, 0, sizeof(t));
-        if (s.kind < 0 || s.kind > 2 || (s.channels != 1 && s.channels != 3)) return bad("bad texture record");
+        if (s.kind < 0 || s.kind > 2) return bad("texture kind out of range");
+        if (s.channels != 1 && s.channels != 3) return bad("texture channels must be 1 or 3");
         t.kind = s.kind; t.channels = s.channels;
         for (int c = 0; c < 3; ++c) { t.value[c] = s.value[c]; t.value2[c] = s.value2[c]; }
         t.su = s.su; t.sv = s.sv; t.du = s.du; t.dv = s.dv; t.wrap = s.wrap;
         if (s.kind == PTRS_TEX_IMAGE) {
-            if (s.n_levels <= 0 || !s.level_data || !s.level_cols || !s.level_rows) return bad("image texture without pyramid");
+            if (s.wrap < PTRS_WRAP_REPEAT || s.wrap > PTRS_WRAP_CLAMP) return bad("image texture wrap out of range"); // (the device would clamp; the description is wrong all the same)
+            if (s.n_levels <= 0) return bad("image texture without levels");
+            if (!s.level_data) return bad("image texture: level_data is NULL");
+            if (!s.level_cols) return bad("image texture: level_cols is NULL");
+            if (!s.level_rows) return bad("image texture: level_rows is NULL");
             t.n_levels = s.n_levels; t.first_level = (uint32_t)H.levels.size();
             for (int l = 0; l < s.n_levels; ++l) {
                 DTexLevel L; L.offset = H.texdata.size(); L.cols = s.level_cols[l]; L.rows = s.level_rows[l];
                 if (L.cols <= 0 || L.rows <= 0) return bad("empty texture level");
+                if (!s.level_data[l]) return bad("image texture: a level's data is NULL");
                 size_t n = (size_t)L.cols * (size_t)L.rows * (size_t)s.channels;
                 H.texdata.insert(H.texdata.end(), s.level_data[l], s.level_data[l] + n);
                 H.levels.push_back(L);
@@ -163,21 +176,25 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
                 for (int c = 0; c < 3; ++c) m.cval[k][c] = d.textures[s.tex[k]].value[c];
             }
         }
-        bool ok = true;
         for (int k = 0; k < 6; ++k) if (s.tex[k] < -1 || (s.tex[k] >= 0 && (uint32_t)s.tex[k] >= d.n_textures)) return bad("material texture id out of range"); // every slot is -1 or a texture, also the ones its kind ignores
-        switch (s.kind) {
-            case PTRS_MAT_MATTE: ok = tex_ok(s.tex[0], 3); break;
-            case PTRS_MAT_MIRROR: break;
-            case PTRS_MAT_GLASS: ok = tex_ok(s.tex[0], 3) && tex_ok(s.tex[1], 3) && tex_ok(s.tex[2], 1); break;
-            case PTRS_MAT_METAL: // u/v roughness: both or neither (pt_material.h prefers them slot by slot); `roughness` is needed for the slots they leave open
-                ok = tex_ok(s.tex[0], 3) && tex_ok(s.tex[1], 3) && tex_ok(s.tex[2], 3) && ((tex_ok(s.tex[4], 1) && tex_ok(s.tex[5], 1)) || (s.tex[4] < 0 && s.tex[5] < 0 && tex_ok(s.tex[3], 1))) && (s.tex[3] < 0 || tex_ok(s.tex[3], 1));
-                break;
-            case PTRS_MAT_DISNEY: ok = tex_ok(s.tex[0], 3) && tex_ok(s.tex[1], 1) && tex_ok(s.tex[2], 1) && tex_ok(s.tex[3], 1); break;
-            case PTRS_MAT_SUBSTRATE: ok = tex_ok(s.tex[0], 3) && tex_ok(s.tex[1], 3) && tex_ok(s.tex[2], 1) && tex_ok(s.tex[3], 1); break;
-            case PTRS_MAT_NORMAL: ok = tex_ok(s.tex[0], 3) && s.inner >= 0 && (uint32_t)s.inner < d.n_materials && (uint32_t)s.inner != i; break;
-            default: err = "unknown material kind"; return PTRS_ERR_UNSUPPORTED;
+        // the slots a kind needs, with their channel counts (0 = not needed); Metal's roughness slots follow below
+        static const int need[7][4] = {{3, 0, 0, 0}, {3, 3, 3, 0}, {0, 0, 0, 0}, {3, 3, 1, 0}, {3, 1, 1, 1}, {3, 3, 1, 1}, {3, 0, 0, 0}};
+        if (s.kind < 0 || s.kind > PTRS_MAT_NORMAL) { err = "unknown material kind"; return PTRS_ERR_UNSUPPORTED; }
+        for (int k = 0; k < 4; ++k) if (need[s.kind][k] && !tex_ok(s.tex[k], need[s.kind][k])) return bad(need[s.kind][k] == 3 ? "material needs a 3-channel texture in a slot that has none" : "material needs a 1-channel texture in a slot that has none");
+        if (s.kind == PTRS_MAT_METAL) { // u/v roughness: both or neither (pt_material.h prefers them slot by slot); `roughness` is needed for the slots they leave open
+            if ((s.tex[4] >= 0) != (s.tex[5] >= 0)) return bad("metal: u_rough and v_rough come both or not at all");
+            for (int k = 3; k < 6; ++k) if (s.tex[k] >= 0 && !tex_ok(s.tex[k], 1)) return bad("metal: roughness textures have 1 channel");
+            if (s.tex[4] < 0 && s.tex[3] < 0) return bad("metal without a roughness texture");
         }
-        if (!ok) return bad("material references a missing texture / inner material");
+        if (s.kind == PTRS_MAT_NORMAL) {
+            if (s.inner < 0 || (uint32_t)s.inner >= d.n_materials) return bad("normal material: inner out of range");
+            if ((uint32_t)s.inner == i) return bad("normal material wraps itself");
+        }
+    }
+    for (uint32_t i = 0; i < d.n_materials; ++i) { // a wrapper reaches a material of another kind within four steps, used by a mesh or not
+        uint32_t mi = i;
+        for (int g = 0; g < 4 && H.mats[mi].kind == PTRS_MAT_NORMAL; ++g) { mi = (uint32_t)H.mats[mi].inner; if (mi == i) return bad("normal materials wrap each other"); }
+        if (H.mats[mi].kind == PTRS_MAT_NORMAL) return bad("normal materials nested too deeply");
     }
     // ---- triangles ------------------------------------------------------------------------------
     std::vector<uint32_t> mesh_first(d.n_meshes);
@@ -187,14 +204,18 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
     H.shade.resize(n_tris);
     for (uint32_t m = 0; m < d.n_meshes; ++m) {
         const PtrsMesh &s = d.meshes[m];
-        if (!s.pos || !s.indices) return bad("mesh without positions / indices");
         if (s.material < 0 || (uint32_t)s.material >= d.n_materials) return bad("mesh material out of range");
         if (s.alpha_mask_tex >= 0 && !tex_ok(s.alpha_mask_tex, 1)) return bad("alpha mask must be a 1-channel texture");
+        if (!s.n_tris) continue; // a mesh without triangles is legal whatever its pointers are, and contributes nothing: no kernel feature, no material bucket
+        if (!s.pos) return bad("mesh with triangles but pos is NULL");
+        if (!s.indices) return bad("mesh with triangles but indices is NULL");
+        if (!s.n_verts) return bad("mesh with triangles but no vertices");
+        for (size_t k = 0; k < 3 * (size_t)s.n_verts; ++k) // the builder bins and orders centroids: a NaN or an infinity has no bin and no order
+            if ((f2u(s.pos[k]) & 0x7f800000u) == 0x7f800000u) { err = "mesh " + std::to_string(m) + " vertex " + std::to_string(k / 3) + ": position is not finite"; return (int)PTRS_ERR_INVALID; }
         if (s.alpha_mask_tex >= 0) H.has_alpha = true;
         int mi = s.material;
         for (int g = 0; g < 4 && H.mats[mi].kind == PTRS_MAT_NORMAL; ++g) mi = H.mats[mi].inner;
-        const int bucket = H.mats[mi].kind;
-        if (bucket == PTRS_MAT_NORMAL) return bad("normal materials nested too deeply");
+        const int bucket = H.mats[mi].kind; // (never NORMAL: the materials' own check above)
         H.kinds_present[bucket] = true;
         for (uint32_t t = 0; t < s.n_tris; ++t) {
             DTriShade &T = H.shade[mesh_first[m] + t];
@@ -239,7 +260,9 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
         for (int c = 0; c < 3; ++c) { L.v[c] = s.v[c]; L.c[c] = s.c[c]; }
         L.world_radius = s.world_radius;
         if (s.kind == PTRS_LIGHT_AREA) {
-            if (s.mesh >= d.n_meshes || s.tri >= d.meshes[s.mesh].n_tris || !tex_ok(s.ke_tex, 3)) return bad("bad area light record");
+            if (s.mesh >= d.n_meshes) return bad("area light: mesh out of range");
+            if (s.tri >= d.meshes[s.mesh].n_tris) return bad("area light: triangle out of range");
+            if (!tex_ok(s.ke_tex, 3)) return bad("area light: ke_tex must be a 3-channel texture");
             L.tri = (int32_t)(mesh_first[s.mesh] + s.tri); L.ke_tex = s.ke_tex;
             DTriShade &T = H.shade[L.tri];
             T.light = (int32_t)i; T.flags |= TRI_IS_LIGHT;
@@ -247,7 +270,12 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
             L.area = 0.5f * len(cross(q1 - q0, q2 - q0)); // Triangle::area, shape.rs:533-539
             if (d.textures[s.ke_tex].kind == PTRS_TEX_CONSTANT) { L.ke_const = 1u; for (int c = 0; c < 3; ++c) L.c[c] = d.textures[s.ke_tex].value[c]; }
         } else if (s.kind == PTRS_LIGHT_INFINITE) {
-            if (!tex_ok(s.lmap_tex, 3) || d.textures[s.lmap_tex].kind != PTRS_TEX_IMAGE || s.dist_nu <= 0 || s.dist_nv <= 0 || !s.dist_func || !s.dist_cdf || !s.dist_func_int || !s.marg_cdf) return bad("bad infinite light record");
+            if (!tex_ok(s.lmap_tex, 3) || d.textures[s.lmap_tex].kind != PTRS_TEX_IMAGE) return bad("infinite light: lmap_tex must be a 3-channel image texture");
+            if (s.dist_nu <= 0 || s.dist_nv <= 0) return bad("infinite light: distribution without rows or columns");
+            if (!s.dist_func) return bad("infinite light: dist_func is NULL");
+            if (!s.dist_cdf) return bad("infinite light: dist_cdf is NULL");
+            if (!s.dist_func_int) return bad("infinite light: dist_func_int is NULL");
+            if (!s.marg_cdf) return bad("infinite light: marg_cdf is NULL");
             L.lmap_tex = s.lmap_tex;
             std::memcpy(L.l2w, s.light_to_world, 48); std::memcpy(L.w2l, s.world_to_light, 48);
             L.nu = s.dist_nu; L.nv = s.dist_nv; L.marg_int = s.marg_func_int;
@@ -312,15 +340,29 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
         H.nodes.resize(d.n_bvh_nodes);
         std::memcpy(H.nodes.data(), d.bvh_nodes, sizeof(DNode) * d.n_bvh_nodes);
         order.assign(d.bvh_prims, d.bvh_prims + n_tris);
-        for (auto &nd : H.nodes) { // validate indices so that a bad tree cannot fault the GPU
-            uint32_t np = nd.meta & 0xffffu;
-            if (np ? (nd.offset + np > n_tris) : (nd.offset >= d.n_bvh_nodes)) return bad("bvh node out of range");
-            if (!np && ((nd.meta >> 16) & 0xffu) > 2) return bad("bvh axis out of range");
+        // validate the tree so that it cannot fault the GPU or hang the host: every index in range (in 64 bits: offset + num_prims of two
+        // 32-bit values wraps), then a walk that marks nodes -- each node is reached exactly once from the root, so the records are a
+        // tree, the walk and the conversions below take one step per node, and the depth bound is kept
+        for (uint32_t i = 0; i < d.n_bvh_nodes; ++i) {
+            const DNode &nd = H.nodes[i];
+            const uint32_t np = nd.meta & 0xffffu;
+            if (np) { if ((uint64_t)nd.offset + (uint64_t)np > (uint64_t)n_tris) return bad("bvh leaf range out of bounds"); continue; }
+            if (nd.offset >= d.n_bvh_nodes) return bad("bvh child index out of range");
+            if (i + 1 >= d.n_bvh_nodes) return bad("bvh interior node in the last record has no first child");
+            if (((nd.meta >> 16) & 0xffu) > 2) return bad("bvh axis out of range");
         }
         for (uint32_t p : order) if (p >= n_tris) return bad("bvh prim out of range");
-        // depth by walking the depth-first layout
+        std::vector<char> reached(d.n_bvh_nodes, 0);
         std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0, 1});
-        while (!st.empty()) { auto [i, dp] = st.back(); st.pop_back(); H.max_depth = std::max(H.max_depth, dp); const DNode &nd = H.nodes[i]; if (!(nd.meta & 0xffffu)) { if (i + 1 >= d.n_bvh_nodes || dp > 4096) return bad("bvh malformed"); st.push_back({i + 1, dp + 1}); st.push_back({nd.offset, dp + 1}); } }
+        while (!st.empty()) {
+            auto [i, dp] = st.back(); st.pop_back();
+            if (reached[i]) return bad("bvh node reached twice");
+            reached[i] = 1;
+            if (dp > 4096) return bad("bvh deeper than 4096 levels");
+            H.max_depth = std::max(H.max_depth, dp);
+            if (!(H.nodes[i].meta & 0xffffu)) { st.push_back({i + 1, dp + 1}); st.push_back({H.nodes[i].offset, dp + 1}); }
+        }
+        for (char r : reached) if (!r) return bad("bvh node never reached");
     } else if (n_tris) {
         hostbvh::Builder B; B.nodes = &H.nodes; B.items.resize(n_tris);
         for (size_t i = 0; i < n_tris; ++i) {
@@ -476,8 +518,28 @@ inline int build_host_scene(const PtrsSceneDesc &d, HostScene &H, std::string &e
         H.max_depth = std::max(H.max_depth, depth2 + 1);
         stack_bound2 = depth2;
     }
+    // ---- a scene without a triangle ----
+    // The traversal kernels start every ray at record 0 of the layout and have no test for "no record" (the LDS form would read
+    // planes and references from LDS that nothing wrote).  So the layout of an empty scene holds ONE record that no ray can enter:
+    // a pair node whose first child has the box (min = +inf, max = -inf) and whose second child is absent -- the LDS form stages
+    // the same box for an absent child --, or a quad node of four empty slots.  Both slab tests end with the largest lower end
+    // +inf and the smallest upper end -inf for every finite origin and any direction (infinite reciprocals included; a NaN product
+    // on an axis is dropped by max / min or fails the box through the x-axis test): no child is entered, nothing is pushed, and the
+    // pop from the ray's empty stack gives REF_NONE: the ray ends as a miss after one visit.  No reference of the record is ever followed.
+    if (H.nodes.empty()) {
+        DNode2 e; std::memset(&e, 0, sizeof(e));
+        e.c0min[0] = e.c0min[1] = e.c0min[2] = PT_INF; e.c0max0 = e.c0max1 = e.c0max2 = -PT_INF;
+        e.c1min0 = e.c1min1 = e.c1min2 = PT_INF; e.c1max[0] = e.c1max[1] = e.c1max[2] = -PT_INF;
+        e.ref0 = REF_NONE; e.ref1 = REF_NONE; e.axis = 3;
+        H.nodes2.assign(1, e);
+        DNode4 q; std::memset(&q, 0, sizeof(q));
+        for (int s = 0; s < 4; ++s) { q.ref[s] = REF_NONE; for (int k = 0; k < 3; ++k) { q.box[(2 * k) * 4 + s] = PT_INF; q.box[(2 * k + 1) * 4 + s] = -PT_INF; } }
+        q.axes = 3u | (3u << 2) | (3u << 4); // never swap, no occupied slot; pad[0] = 0: no split axis
+        H.nodes4.assign(1, q);
+        H.max_depth = 1; stack_bound2 = 1; stack_bound4 = 3; // what a tree of one record gives below: nothing is ever stacked
+    }
     // small scenes are walked out of LDS in pair form (cheaper steps when a fetch costs nothing), the rest in quad form
-    H.use_quad = 7u * H.nodes2.size() + 9u * n_tris > PAIR_FORM_MAX_V4;
+    H.use_quad =7u * H.nodes2.size() + 9u * n_tris > PAIR_FORM_MAX_V4;
     if (node_form == 2) H.use_quad = true; // (pair form cannot be forced: the kernels only walk it out of LDS)
     if (H.use_quad) { H.nodes2.clear(); H.stack_bound = stack_bound4; } else { H.nodes4.clear(); H.stack_bound = stack_bound2; }
     if (H.use_quad && H.nodes4.size() > QUAD_TOP_NODES) {
@@ -529,7 +591,7 @@ inline DScene host_scene_view(const HostScene &H) {
     sc.nodes2 = H.nodes2.data(); sc.n_nodes2 = (uint32_t)H.nodes2.size(); sc.nodes4 = H.nodes4.data(); sc.n_nodes4 = (uint32_t)H.nodes4.size();
     sc.nodes = H.nodes.data(); sc.tris = H.tris.data(); sc.shade = H.shade.data(); sc.mats = H.mats.data(); sc.texs = H.texs.data();
     sc.levels = H.levels.data(); sc.texdata = H.texdata.data(); sc.lights = H.lights.data(); sc.distdata = H.distdata.data(); sc.inf_lights = H.inf_lights.data();
-    sc.n_nodes = (uint32_t)H.nodes.size(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
+    sc.n_nodes = H.reported_nodes(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
     return sc;
 }
 

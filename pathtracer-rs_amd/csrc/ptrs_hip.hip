@@ -2493,12 +2493,13 @@ int ptrs_get_option(const char *name, int64_t *value) {
 
 static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScene **out) {
     if (!desc || !out) { g_err = "null argument"; return PTRS_ERR_INVALID; }
-    int rc = select_device(device);
-    if (rc != PTRS_OK) return rc;
+    // the description is checked, and the host copy built, before the first device call: a malformed one is refused on a machine without a GPU too
     std::unique_ptr<PtrsScene> ps(new PtrsScene());
     ps->device = device;
     const Options opt = options();
-    if ((rc = build_host_scene(*desc, ps->H, g_err, opt.node_form, opt.node_order)) != PTRS_OK) return rc;
+    int rc = build_host_scene(*desc, ps->H, g_err, opt.node_form, opt.node_order);
+    if (rc != PTRS_OK) return rc;
+    if ((rc = select_device(device)) != PTRS_OK) return rc;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ps->n_cu = prop.multiProcessorCount;
     HostScene &H = ps->H;
@@ -2510,7 +2511,7 @@ static int scene_create_impl(const PtrsSceneDesc *desc, int32_t device, PtrsScen
     sc.nodes = (const DNode *)ps->nodes.p; sc.tris = (const DTri *)ps->tris.p; sc.shade = (const DTriShade *)ps->shade.p; sc.mats = (const DMaterial *)ps->mats.p;
     sc.texs = (const DTexture *)ps->texs.p; sc.levels = (const DTexLevel *)ps->levels.p; sc.texdata = (const float *)ps->texdata.p; sc.lights = (const DLight *)ps->lights.p;
     sc.distdata = (const float *)ps->distdata.p; sc.inf_lights = (const uint32_t *)ps->inf.p;
-    sc.n_nodes = (uint32_t)H.nodes.size(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
+    sc.n_nodes = H.reported_nodes(); sc.n_prims = (uint32_t)H.tris.size(); sc.n_lights = (uint32_t)H.lights.size(); sc.n_inf = (uint32_t)H.inf_lights.size();
     // traversal stack: 8 LDS entries per lane; what a deeper tree can stack beyond that spills to a global column per
     // resident thread.  Quad-form scenes spend the LDS this saves on the top QUAD_TOP_NODES records of the tree (measured
     // against a 16-entry column without the cache: +2 % on colonnade, +1 % on classroom).  the option stack_lds = 16 selects that
@@ -2536,7 +2537,7 @@ void ptrs_scene_destroy(PtrsScene *scene) {
 
 int ptrs_scene_info(PtrsScene *scene, uint64_t *n_nodes, uint64_t *max_depth, uint64_t *n_tris) {
     if (!scene) { g_err = "null scene"; return PTRS_ERR_INVALID; }
-    if (n_nodes) *n_nodes = scene->H.nodes.size();
+    if (n_nodes) *n_nodes = scene->H.reported_nodes();
     if (max_depth) *max_depth = scene->H.max_depth;
     if (n_tris) *n_tris = scene->H.tris.size();
     return PTRS_OK;

@@ -394,13 +394,21 @@ class RenderScene:
         self.lights.append(dict(kind=abi.LIGHT_DIRECTIONAL, v=w, c=radiance))
 
     def world_bound(self):
-        lo = np.min([np.asarray(m["pos"], dtype=np.float32).reshape(-1, 3).min(axis=0) for m in self.meshes], axis=0)
-        hi = np.max([np.asarray(m["pos"], dtype=np.float32).reshape(-1, 3).max(axis=0) for m in self.meshes], axis=0)
+        """The bound of the meshes that have triangles (a mesh without one contributes nothing); None for a scene without geometry."""
+        boxes = [np.asarray(m["pos"], dtype=np.float32).reshape(-1, 3) for m in self.meshes if len(m["indices"])]
+        if not boxes:
+            return None
+        lo = np.min([b.min(axis=0) for b in boxes], axis=0)
+        hi = np.max([b.max(axis=0) for b in boxes], axis=0)
         return lo, hi
 
     def preprocess_lights(self):
-        """Light::preprocess (light.rs:209-211,480-482) with Bounds3::bounding_sphere (bounds.rs:126-134)."""
-        lo, hi = self.world_bound()
+        """Light::preprocess (light.rs:209-211,480-482) with Bounds3::bounding_sphere (bounds.rs:126-134).  A scene without geometry has
+        no bound to derive a sphere from: its lights keep the world_center / world_radius their records carry."""
+        bound = self.world_bound()
+        if bound is None:
+            return
+        lo, hi = bound
         center = (lo + hi) * F(0.5)
         d = center - hi
         radius = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
